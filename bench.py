@@ -3,13 +3,20 @@ exact sequential stream, measured through libqsched's C ABI on MI355X.
 
 Workloads (BASELINE.json configs):
   * N = 1 (default): configs[1] — 5,000 nodes × 100,000 pods on one GPU (the metric's config).
-    The line also carries a ``config3`` object: the 50,000-node × 1,000,000-pod stream on the same
-    single GPU, the N = 1 point of the config-3 scaling curve.
+    With ``--full`` the line also carries a ``config3`` object: the 50,000-node × 1,000,000-pod
+    stream on the same single GPU, the N = 1 point of the config-3 scaling curve.
   * N > 1 (torchrun, one rank per GPU): configs[2] — 50,000 nodes × 1,000,000 pods with the node
     table sharded across the N ranks (qs_open_shard: contiguous node ranges, one exchange of
     top-L lists per lookahead window over xGMI: the peer-memory mailbox by default, an RCCL
     all-gather with ``--transport rccl``).  Total work is fixed: ``scaling`` = "strong".
   ``--workload config2|config3`` overrides (config2 at N > 1 = independent replicas, weak scaling).
+
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps and prints the
+result line with the headline figure alone.  ``--full`` adds everything else the benchmark measures
+or checks: the per-pod latency and per-kernel diagnostic runs with the roofline, the oracle checks,
+the config 3 / 4 / 5, scan, end-to-end, framework-path and wide-layout legs, the per-pod RCCL leg
+and the CPU baselines.  ``--dump-outputs DIR`` writes what the last timed step computed (placements,
+per-pod keys, the node table after the stream) as ``DIR/<name>.npy``.
 
 A *step* = restore the empty cluster on the device (qs_table_restore, a D2D copy) + run the whole
 exact stream (qs_stream_run): inputs resident in HBM, every pod scheduled, placements left in HBM.
@@ -73,6 +80,11 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="auto", choices=["auto", "config2", "config3"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostic runs (latency percentiles, per-kernel times, roofline), the "
+                         "oracle checks, the other configurations' legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--engine", default="auto")
     ap.add_argument("--lookahead", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=0,
@@ -505,7 +517,7 @@ def measure_sharded(cx, a, workload):
         TRANSPORT["name"] = name
         m, err = None, None
         try:
-            m = measure(cx, a, workload, a.steps, a.warmup)
+            m = measure(cx, a, workload, a.steps, a.warmup, with_diag=a.full)
         except Exception as e:  # a timed-out or failed exchange on this rank
             err = repr(e)[:300]
         ok = cx.min(1.0 if m is not None else 0.0) > 0
@@ -812,6 +824,33 @@ def run_leg(cx, a, leg):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20  # all of --dump-outputs' files together
+
+
+def dump_outputs(m, out_dir):
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files:
+    the placements (node index per pod, -1 = unschedulable), the per-pod winning keys (uint64,
+    written as their high and low 32-bit halves so that every bit survives float64) and the integer
+    quantity columns of the node table after the stream (the uint64 taint / label masks are inputs
+    the stream never writes).  Above DUMP_MAX_BYTES in all, every array is cut to the same share of
+    the budget by a fixed, seeded sample of its rows (in index order)."""
+    keys = np.asarray(m["keys"], np.uint64)
+    arrays = {"placement": m["placement"], "keys_hi": keys >> np.uint64(32),
+              "keys_lo": keys & np.uint64(0xFFFFFFFF)}
+    for k, v in m["final"].items():
+        if v.dtype.kind == "i":
+            arrays[f"table_{k}"] = v
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(len(v) * (DUMP_MAX_BYTES / total) * 0.99))
+            idx = np.sort(np.random.default_rng(0x5EED).choice(len(v), keep, replace=False))
+            v = v[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+
+
 def main():
     argv = sys.argv[1:]
     a = parse(argv)
@@ -841,9 +880,11 @@ def main():
     if cx.world > 1 and workload == "config3":
         m = measure_sharded(cx, a, workload)
     else:
-        m = measure(cx, a, workload, a.steps, a.warmup)
+        m = measure(cx, a, workload, a.steps, a.warmup, with_diag=a.full)
+    if a.dump_outputs and cx.rank == 0:
+        dump_outputs(m, a.dump_outputs)
     rccl = None
-    if workload == "config3" or (cx.world == 1 and not a.no_config3):
+    if a.full and (workload == "config3" or (cx.world == 1 and not a.no_config3)):
         if a.rccl_sample > 0:
             progress(f"per-pod RCCL all-reduce leg ({a.rccl_sample} pods)")
             try:
@@ -851,7 +892,7 @@ def main():
             except Exception as e:  # reported, not fatal (every rank fails it at the same point)
                 rccl = {"error": repr(e)[:300]}
     c3 = c4 = c4g = c5 = scan = None
-    if cx.world == 1 and workload == "config2" and not a.no_config3:
+    if a.full and cx.world == 1 and workload == "config2" and not a.no_config3:
         progress("config3 leg")
         c3 = measure(cx, a, "config3", 1, 1, with_diag=False)
         progress("config4 leg")
@@ -860,18 +901,16 @@ def main():
         c4g = measure(cx, a, "config4_gpu_scoring", 3, 1, with_diag=True)
         progress("config5 leg")
         c5 = measure(cx, a, "config5", 3, 1, with_diag=False)
-    if cx.world == 1 and not a.no_scan:
+    if a.full and cx.world == 1 and not a.no_scan:
         progress("scan roofline leg")
         scan = scan_roofline(cx, a)
     e2e = fw = wide = None
-    if cx.world == 1 and workload == "config2" and not a.no_extra:
+    if a.full and cx.world == 1 and workload == "config2" and not a.no_extra:
         progress("end-to-end, framework and wide legs")
         e2e = e2e_leg(cx, m["nodes"], m["pods"], m["placement"])
         fw = framework_leg(cx)
         wide = wide_leg(cx, a)
     if cx.rank == 0:
-        rl = roofline(m["kp"], m["n_nodes"], m["n_pods"], m["wall_fallback"],
-                      inst="<0u," if not m["sharded"] and workload == "config2" else None)
         if m["sharded"]:
             how = ("RCCL all-gather per window" if TRANSPORT["name"] == "rccl" else
                    "peer-memory mailbox, shard lists exchanged in-launch" if m["launch"] == "resident" else
@@ -892,18 +931,21 @@ def main():
                        "table_layout": m["table_layout"],
                        "lookahead": a.lookahead or 32, "parallelism": par},
             "evals_per_s": round(m["value"] * m["n_nodes"], 1),
-            "p50_pod_latency_us": round(m["p50"], 4), "p99_pod_latency_us": round(m["p99"], 4),
-            "p99_pod_latency_split_us": {k: (round(v, 4) if v is not None else None)
-                                         for k, v in (m.get("p99_split") or {}).items()},
             "unschedulable_frac": round(m["unschedulable_frac"], 5),
-            "roofline": rl,
-            "kernels_us_per_step": {k: round(v["s"] * 1e6, 1) for k, v in m["kp"].items()},
         }
+        if a.full:  # from the untimed diagnostic runs
+            out["p50_pod_latency_us"] = round(m["p50"], 4)
+            out["p99_pod_latency_us"] = round(m["p99"], 4)
+            out["p99_pod_latency_split_us"] = {k: (round(v, 4) if v is not None else None)
+                                               for k, v in (m.get("p99_split") or {}).items()}
+            out["roofline"] = roofline(m["kp"], m["n_nodes"], m["n_pods"], m["wall_fallback"],
+                                       inst="<0u," if not m["sharded"] and workload == "config2" else None)
+            out["kernels_us_per_step"] = {k: round(v["s"] * 1e6, 1) for k, v in m["kp"].items()}
         if m.get("transport"):
             out["config"]["transport"] = m["transport"]
             if m["transport_tried"]:
                 out["config"]["transport_fallback_from"] = m["transport_tried"]
-        if m["sharded"] or (cx.world == 1 and not a.no_cpu):
+        if a.full and (m["sharded"] or (cx.world == 1 and not a.no_cpu)):
             progress("oracle check of the timed stream")
             out["check"] = check_stream(m)
         if rccl is not None:
@@ -949,7 +991,7 @@ def main():
             out["end_to_end"] = e2e
             out["framework_path"] = fw
             out["wide_layout"] = wide
-        if cx.world == 1 and not a.no_cpu:
+        if a.full and cx.world == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_baseline(m["nodes"], m["pods"], m["n_nodes"], m["n_pods"],
                                                a.cpu_sample, gpu_placement=m["placement"])
             out["cpu_baseline_parallel"] = cpu_baseline(m["nodes"], m["pods"], m["n_nodes"], m["n_pods"],

@@ -243,7 +243,7 @@ def _rank_measure_fail(rank, port, q, fail):
 
     qsched.Scheduler = Sched
     cx = bench.Ctx(backend="gloo")
-    a = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    a = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])  # the diagnostic runs too
     m = bench.measure_sharded(cx, a, "config3")
     cx.dist.destroy_process_group()
     q.put((rank, m["transport"], [t["transport"] for t in m["transport_tried"]]))
@@ -285,6 +285,68 @@ def test_cpu_arms_capped_by_the_process_share(monkeypatch):
     assert bench.effective_cpus() == 256
 
 
+def test_plain_run_times_the_steps_and_dumps_outputs(monkeypatch, capsys, tmp_path):
+    """A plain run (no --full) over a CPU fake of the library's Scheduler: warmup + steps stream
+    runs and nothing else, the headline line with ms_per_step, and --dump-outputs' float64 files
+    holding the last step's placements, keys (exact through the two 32-bit halves) and table."""
+    import numpy as np
+
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "custom-k8s-scheduler_amd")]
+    import bench
+    import qsched
+
+    monkeypatch.setitem(bench.WORKLOADS, "config2", (2, 300, 2000, "config2 (small, fake scheduler)"))
+    monkeypatch.setattr(qsched, "Scheduler", _fake_scheduler_cls(0, None))
+    monkeypatch.setattr(_FakeStream, "results", lambda self: (
+        np.arange(len(self.pods), dtype=np.int32) % 7 - 1,
+        np.arange(len(self.pods), dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    out = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2",
+                                      "--dump-outputs", str(out)])
+    _RUNS[0] = 0
+    assert bench.main() == 0
+    assert _RUNS[0] == 5  # 2 warm-up + 3 timed steps: no diagnostic run, no other leg
+    line = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["unit"] == "pods/s" and line["higher_is_better"] is True and line["dtype"] == "int32+f64"
+    for k in ("roofline", "check", "cpu_baseline", "config3", "scan", "rccl_per_pod", "p99_pod_latency_us"):
+        assert k not in line
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(v.dtype == np.float64 for v in files.values())
+    assert sum(v.nbytes for v in files.values()) <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(files["placement"], np.arange(2000) % 7 - 1)
+    keys = (files["keys_hi"].astype(np.uint64) << np.uint64(32)) | files["keys_lo"].astype(np.uint64)
+    assert np.array_equal(keys, np.arange(2000, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15))
+    nodes, _ = qsched.synth_generate(2, 300, 2000, seed=0x5EED0002)
+    assert np.array_equal(files["table_alloc_mem"], nodes["alloc_mem"])  # (the fake leaves the table as loaded)
+
+
+def test_dump_outputs_samples_above_the_size_limit(monkeypatch, tmp_path):
+    """Above DUMP_MAX_BYTES every array is cut by the same seeded row sample, identical run to run."""
+    import numpy as np
+
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "custom-k8s-scheduler_amd")]
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10000)
+    m = {"placement": np.arange(3000, dtype=np.int32), "keys": np.arange(3000, dtype=np.uint64),
+         "final": {"pods": np.arange(500, dtype=np.int64), "taint_hard": np.zeros(500, np.uint64)}}
+    bench.dump_outputs(m, str(tmp_path / "a"))
+    bench.dump_outputs(m, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["keys_hi.npy", "keys_lo.npy", "placement.npy", "table_pods.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert np.array_equal(x, y) and x.dtype == np.float64 and 0 < len(x)
+        total += x.nbytes
+    assert total <= 10000
+    pl = np.load(tmp_path / "a" / "placement.npy")
+    assert np.all(np.diff(pl) > 0) and len(pl) < 3000  # a sample of the rows, in index order
+
+
 def _rank_line(rank, port, q):
     """bench.main() at world 2 over gloo (config 3 small, a CPU fake of the library's Scheduler):
     the rank-0 line must carry the sharded mailbox measurement AND the per-pod RCCL all-reduce
@@ -302,7 +364,7 @@ def _rank_line(rank, port, q):
     bench.WORKLOADS["config3"] = (3, 300, 2000, "config3 (small, fake scheduler)")
     qsched.dist_unique_id = lambda: bytes(range(128))
     qsched.Scheduler = _fake_scheduler_cls(rank, None)
-    sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rccl-sample", "400"]
+    sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rccl-sample", "400", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main()

@@ -7,8 +7,8 @@ TAG=${1:-r01}
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT profiles
-ARGS="--steps 2 --warmup 1 --no-cpu"  # config 3 included: its k_la_stream_res row
-PMC_ARGS="--steps 1 --warmup 1 --no-cpu --no-extra"  # the scan leg too
+ARGS="--full --steps 2 --warmup 1 --no-cpu"  # config 3 included: its k_la_stream_res row
+PMC_ARGS="--full --steps 1 --warmup 1 --no-cpu --no-extra"  # the scan leg too
 # heartbeat for the GPU pool's silence watchdog (counter passes print nothing for minutes)
 ( while sleep 45; do date >> $OUT/heartbeat; done ) &
 HB=$!

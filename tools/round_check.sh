@@ -12,4 +12,5 @@ fi
 NOWIN=1 bash tools/res_check.sh || exit 1
 grep -q "tests rc=0" gpurun_out/rc_tests.log || exit 1
 [ -n "$NOPROF" ] || bash tools/profile_fetch.sh $TAG || exit 1
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_$TAG.log 2>&1
+mkdir -p ${RESULTS:-out}
+timeout -k 10 400 python -u bench.py --full > ${RESULTS:-out}/bench_$TAG.log 2>&1
