@@ -124,6 +124,7 @@ struct qs_ctx {
     int shift = 20;  // memory unit 2^shift bytes on the device (compact layout)
     bool wide = false;  // wide layout: f64 memory columns in bytes (DevTable::wrows)
     bool dev_valid = false;
+    uint32_t zero_alloc = 0;  // nodes of the mirror with allocatable cpu or memory 0 (DevCfg::all_alloc)
     qs::DevTable dt{};
     qs::DevCfg dc{};
     qs_host::DevBuf tbl;  // all columns in one allocation
@@ -155,6 +156,7 @@ struct qs_ctx {
     bool res_cooldown = false;
     uint32_t inject_used = 0;  // QS_INJECT_FAULT test hooks already fired on this context (bit per hook)
     bool last_resident = false;  // the last lookahead run was a resident stream
+    int32_t last_res_path = 0;   // ... and its qs_stats::resident_path bits
     int cus = 0;               // compute units of the device (resident stream's selector count)
     uint64_t run_seq = 0;      // lookahead runs of this context (the hand-off's epoch)
     bool last_waits = false;   // the last lookahead run waited on device words (hand-off / mailbox)

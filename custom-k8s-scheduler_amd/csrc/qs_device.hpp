@@ -118,6 +118,11 @@ struct DevCfg {
     // QS_RES_DIAG=1: the resident selectors time their phases too (extra barriers); =2: the
     // resolver's counters only, selectors untouched
     uint32_t sel_diag;
+    // 1 = every node of the table has allocatable cpu > 0 and memory > 0 (set by the host from its
+    // mirror; 0 when in doubt, or QS_FAST_ALLOC=0): the resident ring resolver's key waves then run
+    // the loops whose two-resource scorers skip the zero-allocatable selects (fit_bal_total<F, true>).
+    // 0 runs the generic code.
+    uint32_t all_alloc;
 };
 
 // Resolver prologue: thread 0 spins (s_sleep) until window s0/K's lists are published, then every
@@ -598,13 +603,18 @@ __device__ __forceinline__ ExtTerms ext_terms(const RowX &x, const P &p) {
 
 // LeastAllocated (UP least_allocated.go#leastResourceScorer), NonZeroRequested + pod nz.
 // Branch-free: a resource with alloc == 0 contributes weight 0 (its score is 0 as well).
-template <uint32_t F, class R, class P>
+// FA (two-resource form only; the caller knows that no node has allocatable cpu or memory 0): the
+// effective weights are wc / wm and the reciprocal is yd_both, which is what the selects below give
+// for such a node, so the same operations in the same order.
+template <uint32_t F, bool FA = false, class R, class P>
 __device__ __forceinline__ uint32_t la_score(const R &r, const RowX &x, const P &p, const DevCfg &c) {
     const bool hc = r.ac != 0, hm = r.am != 0;
     const uint32_t sc_c = least_requested(r.ac, r.zc + p.zc, r.yc);
     uint32_t sc_m;
     if constexpr (std::is_same<R, RowW>::value) sc_m = least_requested_w(r.am, r.zm + p.zm, r.ym);
     else sc_m = least_requested(r.am, r.zm + p.zm, r.ym);
+    if constexpr (FA && (F & kFeatRes) == 0)
+        return floor_div(__umul24(sc_c, (uint32_t)c.wc) + __umul24(sc_m, (uint32_t)c.wm), c.yd_both);
     const uint32_t wce = hc ? (uint32_t)c.wc : 0u, wme = hm ? (uint32_t)c.wm : 0u;
     const uint32_t num = __umul24(sc_c, wce) + __umul24(sc_m, wme);
     if constexpr ((F & kFeatRes) != 0) {
@@ -629,7 +639,7 @@ __device__ __forceinline__ uint32_t la_score(const R &r, const RowX &x, const P 
     }
 }
 // BalancedAllocation (UP balanced_allocation.go#balancedResourceScorer), Requested + pod req
-template <uint32_t F, class R, class P>
+template <uint32_t F, bool FA = false, class R, class P>
 __device__ __forceinline__ uint32_t ba_score(const R &r, const RowX &x, const P &p, const DevCfg &c) {
     const bool hc = r.ac != 0, hm = r.am != 0;
     const double f0 = fraction(r.ac, r.rc + p.rc, r.yc);
@@ -670,7 +680,7 @@ __device__ __forceinline__ uint32_t ba_score(const R &r, const RowX &x, const P 
         }
     } else {
         (void)x;
-        if (hc & hm) sd = __builtin_fabs((f0 - f1) / 2);
+        if (FA || (hc & hm)) sd = __builtin_fabs((f0 - f1) / 2);
     }
     const double scaled = (1 - sd) * 100.0;
     uint32_t ba = (uint32_t)(int32_t)scaled;  // int64() truncation toward zero
@@ -717,6 +727,16 @@ __device__ __forceinline__ uint32_t norm_total(const R &r, const RowX &x, const 
     if (F & kFeatTaint) total += __umul24((uint32_t)c.wtt, tt_norm((st >> 1) & 127u, mt, ymt));
     if (F & kFeatAffinity) total += __umul24((uint32_t)c.wna, na_norm(st >> 8, ma, yma));
     return total;
+}
+// p.wfit * LeastAllocated + p.wbal * BalancedAllocation for the resident ring resolver's key waves.
+// FA: the role's loop was entered on the wave-uniform kernel argument c.all_alloc (no node with
+// allocatable cpu or memory 0), so the two-resource scorers skip the zero-allocatable selects.  The
+// choice is made once per role, outside the step loop: a branch inside the step split the key chain's
+// basic block and cost more than the selects.
+template <uint32_t F, bool FA, class R, class P>
+__device__ __forceinline__ uint32_t fit_bal_total(const R &r, const RowX &x, const P &p, const DevCfg &c) {
+    return __umul24((uint32_t)p.wfit, la_score<F, FA>(r, x, p, c)) +
+           __umul24((uint32_t)p.wbal, ba_score<F, FA>(r, x, p, c));
 }
 // The resolver's lost-holder flags of an infeasible node (bit 0: its taint raw score is the pod's
 // selection-time maximum, bit 1: its affinity raw score is), from static_raw.

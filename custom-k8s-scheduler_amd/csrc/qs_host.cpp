@@ -157,6 +157,18 @@ int table_shift(const Mirror &m) {
     return s;
 }
 
+// Nodes whose allocatable cpu or memory is 0 (qs_ctx::zero_alloc; DevCfg::all_alloc is set for a
+// launch when there are none).  Kept wherever allocatable values enter the mirror: the load scans
+// like table_shift, an upsert adjusts the count by its row, a restore recounts the snapshot's
+// mirror.  Reservations and the kernels never change an allocatable column.  Every rank of a sharded
+// context loads the whole table, so its count covers every rank's nodes.
+bool zero_alloc_row(const Mirror &m, uint32_t i) { return m.ac[i] <= 0 || m.am[i] <= 0; }
+uint32_t count_zero_alloc(const Mirror &m) {
+    uint32_t z = 0;
+    for (uint32_t i = 0; i < m.n; i++) z += zero_alloc_row(m, i) ? 1u : 0u;
+    return z;
+}
+
 void check_range(int64_t v, const char *what, uint32_t i, int64_t limit = kLimit) {
     if (v < 0 || v > limit)
         fail(QS_EINVAL, std::string("node ") + std::to_string(i) + ": " + what + " = " + std::to_string(v) +
@@ -915,6 +927,7 @@ qs_status qs_nodes_load(qs_ctx *c, const qs_node_soa *nd, uint32_t n) {
         }
         for (uint32_t i = 0; i < n; i++) check_row_values(m, i);
         c->shift = table_shift(m);
+        c->zero_alloc = count_zero_alloc(m);
         c->wide = false;
         for (uint32_t i = 0; i < n && !c->wide; i++) c->wide = !row_compact_ok(m, i, c->shift);
         c->dev_valid = false;
@@ -965,6 +978,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         one.zone[0] = r->zone;
         one.gen[0] = generation;
         check_row_values(one, 0);
+        const bool was_zero = idx < m.n && zero_alloc_row(m, idx);
         if (idx == m.n) {  // append one node
             Mirror old = m;
             m.resize(old.n + 1);
@@ -980,6 +994,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
             c->saved = false;
         }
         put_row(m, idx, snap_row(one, 0));
+        c->zero_alloc += (zero_alloc_row(m, idx) ? 1u : 0u) - (was_zero ? 1u : 0u);
         ++c->table_epoch;
         // the new row's memory may need a finer unit or the wide layout (re-upload), else one row
         const int want = std::min({ctz64(r->alloc_mem), ctz64(r->req_mem), ctz64(r->nz_mem)});
@@ -1642,6 +1657,10 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                 // epl > 1 — unless QS_NORM_WAVES=1 pins the single-wave path)
                 LaGeom pgeo = geo;
                 if (norm && overlap && !(nw && nw[0] == '1')) pgeo.waves = 4;
+                // QS_RES_K32=0: the resident resolver's 64-bit key path (read per run: tests and
+                // A/B timing run both widths from one library)
+                const char *rk = getenv("QS_RES_K32");
+                if (rk && rk[0] == '0') pgeo.k32 = 0;
                 LaGeom rgeo = la_stream_res_plan(pgeo, c->dc.feat, n, (uint32_t)c->cus, 2);
                 if (rgeo.G > 0 && rgeo.K * rgeo.G + 1 > la_stream_res_max_blocks(rgeo, c->dc.feat, n, (uint32_t)c->cus))
                     rgeo = la_stream_res_plan(pgeo, c->dc.feat, n, (uint32_t)c->cus, 1);
@@ -1703,6 +1722,14 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                     if (inj && std::strcmp(inj, "resident_skew") == 0) dcr.inject = 2u;
                     // sharded: window 0's waits cover a peer still in host-side prepare (5 s)
                     dcr.first_ticks = c->world > 1 ? 500000000ull : 0ull;
+                    // no node with allocatable cpu or memory 0: the key waves skip those terms
+                    // (QS_FAST_ALLOC=0 keeps the generic scorers; read per run, tests switch it)
+                    const char *fa = getenv("QS_FAST_ALLOC");
+                    dcr.all_alloc = c->zero_alloc == 0 && !(fa && fa[0] == '0') ? 1u : 0u;
+                    // what the launch runs (qs_stats::resident_path): the ring form carries 32-bit
+                    // keys, and its two-resource classes read the flag
+                    c->last_res_path = (!norm && rgeo.k32 ? 1 : 0) |
+                                       (!norm && !(c->dc.feat & kFeatRes) && dcr.all_alloc ? 2 : 0);
                     // QS_RES_DIAG=1: the resolver's time split (list waits / window bodies / between)
                     static const bool rdiag_on = getenv("QS_RES_DIAG") && (getenv("QS_RES_DIAG")[0] == '1' ||
                                                                              getenv("QS_RES_DIAG")[0] == '2');
@@ -1895,6 +1922,7 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
             stats->table_layout = c->wide ? 1 : 0;
             stats->resumed_windows = resumed;
             stats->resident = (eng == QS_ENGINE_LOOKAHEAD && c->last_resident) ? 1 : 0;
+            stats->resident_path = stats->resident ? c->last_res_path : 0;
             stats->device_faults = c->device_faults;
         }
     });
@@ -1949,6 +1977,7 @@ qs_status qs_table_restore(qs_ctx *c) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipMemcpyAsync(c->tbl.p, c->tbl_saved.p, c->tbl.bytes, hipMemcpyDeviceToDevice, c->stream));
         c->m = c->m_saved;        // the mirror of the snapshot
+        c->zero_alloc = count_zero_alloc(c->m);
         c->mirror_stale = false;
         ++c->table_epoch;
         c->soa_valid = false;     // the SoA copy is rebuilt from the restored rows on demand

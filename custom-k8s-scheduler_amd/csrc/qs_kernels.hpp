@@ -32,6 +32,8 @@
 #define QS_EXP_PARK_RETURN()
 #endif
 
+#include "qs_key32.hpp"
+
 namespace qs {
 
 constexpr uint32_t kFeatNorm = kFeatTaint | kFeatAffinity;
@@ -1397,6 +1399,22 @@ __device__ __forceinline__ ResPub read_pub(const ResPub *p) {
     return r;
 }
 
+// The ring resolver's published winner with 32-bit keys (la_resolve4_stream, R32): one
+// ds_write_b128 in wave D, one ds_read_b128 in waves A / B.
+struct alignas(16) ResPub32 {
+    uint32_t k;      // k32 of the winner (0 = unschedulable)
+    int32_t slot;    // existing dirty slot that won, or -1
+    int32_t src;     // lane whose clean candidate won (new slot)
+    uint32_t nd_old; // lane of the new slot
+};
+__device__ __forceinline__ ResPub32 read_pub32(const ResPub32 *p) {
+    const uint4 a = *reinterpret_cast<const uint4 *>(p);
+    return ResPub32{a.x, (int32_t)a.y, (int32_t)a.z, a.w};
+}
+__device__ __forceinline__ void write_pub32(ResPub32 *p, const ResPub32 &v) {
+    *reinterpret_cast<uint4 *>(p) = make_uint4(v.k, (uint32_t)v.slot, (uint32_t)v.src, v.nd_old);
+}
+
 template <uint32_t F, int EPL, bool DIAG, bool K32>
 __device__ __forceinline__ void la_resolve4_block(uint32_t *lds, const DevTable &t, const PodT<F> *__restrict__ pods,
                                                   const DevCfg &c, uint32_t s0, uint32_t P,
@@ -2498,12 +2516,14 @@ constexpr uint32_t kResRing = 4;
 constexpr uint32_t kResTStride = 65;
 constexpr size_t kResLdsMax = 96 * 1024;
 constexpr uint32_t kResSgprMax = 112;  // bound on the resident kernels' sgpr_count (checked: tools/kres.sh)  // dynamic LDS of the resident launch (gfx950: up to 160 KiB per workgroup)  // slot statics [pod][lane] rows, padded: both access patterns conflict-free
+// k32: the ring form's 32-bit keys (keyA / keyB / keyC / C1 and ringE hold 4-byte keys)
 template <uint32_t F>
-constexpr size_t res_stream_lds_bytes(uint32_t n) {
-    size_t b = ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4 + 4 * 2 * 64 * 8 + 2 * 64 * (sizeof(RowT<F>) + sizeof(int4)) +
+constexpr size_t res_stream_lds_bytes(uint32_t n, bool k32) {
+    const size_t kb = (k32 && (F & kFeatNorm) == 0) ? 4 : 8;
+    size_t b = ((((size_t)n + 31) / 32 + 3) & ~(size_t)3) * 4 + 4 * 2 * 64 * kb + 2 * 64 * (sizeof(RowT<F>) + sizeof(int4)) +
                2 * sizeof(ResPub) + 3 * 64 * 4 + 64 * (sizeof(RowT<F>) + sizeof(int4)) + 2 * 64 * sizeof(PodT<F>);
     if ((F & kFeatNorm) == 0)  // the entry / candidate-row rings (kResRing pods) and the late flag
-        b += kResRing * 64 * (8 + sizeof(RowT<F>) + sizeof(int4)) + 16;
+        b += kResRing * 64 * (kb + sizeof(RowT<F>) + sizeof(int4)) + 16;
     if ((F & kFeatNorm) != 0)
         b += 2 * kResNormK * (sizeof(DPodX) + sizeof(NormInfo) + sizeof(double2)) + 2 * 64 * sizeof(RowX) +
              64 * sizeof(RowX) + 64 * (sizeof(RowT<F>) + sizeof(RowX)) + 2 * 64 * 4 + 64 * 4 + 16 * 4 + 8 * 8 + 16 +
@@ -2623,15 +2643,35 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                                                    const DPodX *__restrict__ podx, const NormInfo *norm0,
                                                    const uint32_t *stat0, unsigned long long *nfall) {
     constexpr bool NORM = (F & kFeatNorm) != 0;
+    // R32 (the ring form with 32-bit keys, qs_key32.hpp): every key of the pipeline — list entries in
+    // ringE, C1, keyC, the score halves in keyA / keyB, the published winner, the per-pod result — is
+    // a k32; the lists in global memory and out_key keep the 64-bit format
+    constexpr bool R32 = K32 && !NORM;
+    using KT = typename std::conditional<R32, uint32_t, uint64_t>::type;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t nwords = (t.n + 31) / 32;
     uint32_t *dirty = lds;
     char *base = (char *)(lds + ((nwords + 3) & ~3u));
-    uint64_t(*keyA)[64] = (uint64_t(*)[64])base; base += 2 * 64 * 8;
-    uint64_t(*keyB)[64] = (uint64_t(*)[64])base; base += 2 * 64 * 8;
-    uint64_t(*keyC)[64] = (uint64_t(*)[64])base; base += 2 * 64 * 8;
-    uint64_t(*C1)[64] = (uint64_t(*)[64])base; base += 2 * 64 * 8;
+    KT(*keyA)[64] = (KT(*)[64])base; base += 2 * 64 * sizeof(KT);
+    KT(*keyB)[64] = (KT(*)[64])base; base += 2 * 64 * sizeof(KT);
+    KT(*keyC)[64] = (KT(*)[64])base; base += 2 * 64 * sizeof(KT);
+    KT(*C1)[64] = (KT(*)[64])base; base += 2 * 64 * sizeof(KT);
+    // an entry's / candidate key's node, and a 64-bit list entry in the pipeline's key format
+    auto knode = [](KT k) -> uint32_t {
+        if constexpr (R32) return k32_node(k);
+        else return key_node(k);
+    };
+    auto kconv = [](uint64_t e) -> KT {
+        if constexpr (R32) return k32_from_key(e);
+        else return e;
+    };
+    (void)knode;
+    (void)kconv;
+    // the ring form's key waves (A / B / C) without the zero-allocatable terms: wave-uniform, from the
+    // kernel argument; never for the normalizing or configurable-resource classes
+    constexpr bool kFastAllocClass = !NORM && (F & kFeatRes) == 0;
+    const bool fast_alloc = kFastAllocClass && c.all_alloc != 0u;
     RowT<F>(*stage)[64] = (RowT<F>(*)[64])base; base += 2 * 64 * sizeof(RowT<F>);
     int4(*stagex)[64] = (int4(*)[64])base; base += 2 * 64 * sizeof(int4);
     ResPub *pub = (ResPub *)base; base += 2 * sizeof(ResPub);
@@ -2671,11 +2711,14 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
     // of those entries (ringR / ringX: extended resources), and wave 4's "next window's lists were
     // not there in time" flag for C's boundary fallback
     char *rbase = (char *)(wpodx2);
-    uint64_t(*ringE)[64] = (uint64_t(*)[64])rbase; rbase += kResRing * 64 * 8;
+    KT(*ringE)[64] = (KT(*)[64])rbase; rbase += kResRing * 64 * sizeof(KT);
     RowT<F>(*ringR)[64] = (RowT<F>(*)[64])rbase; rbase += kResRing * 64 * sizeof(RowT<F>);
     int4(*ringX)[64] = (int4(*)[64])rbase; rbase += kResRing * 64 * sizeof(int4);
     uint32_t *late = (uint32_t *)rbase;
     const ResPub none{0, 0xFFFFFFFFu, -1, -1, 0, {0, 0}};
+    // R32: the published winner is 16 bytes in pub's place (waves A / B never read the node)
+    ResPub32 *pub32 = (ResPub32 *)pub;
+    const ResPub32 none32{0u, -1, -1, 0u};
     const DPodX px{};
     // the LeastAllocated weights and weight-sum reciprocals held in VGPRs: the score's per-lane
     // selects then read them directly (gfx950 VALU takes one scalar operand: from SGPRs every
@@ -2700,9 +2743,12 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
 
     for (uint32_t i = threadIdx.x; i < nwords; i += 256) dirty[i] = 0;
     if (threadIdx.x < min(K, P)) wpods2[0][threadIdx.x] = pods[threadIdx.x];
-    if (threadIdx.x == 0) pub[1] = none;
+    if (threadIdx.x == 0) {
+        if constexpr (R32) pub32[1] = none32;
+        else pub[1] = none;
+    }
     if constexpr (!NORM) {  // RING: no entry yet (wave 5 may read a slot before its first write)
-        for (uint32_t j = threadIdx.x; j < kResRing * 64; j += 256) (&ringE[0][0])[j] = 0ull;
+        for (uint32_t j = threadIdx.x; j < kResRing * 64; j += 256) (&ringE[0][0])[j] = 0;
         if (threadIdx.x == 0) *late = 1u;  // window 0: C fetches its first entries and row
     }
     if constexpr (NORM) {  // window 0's pod extension records
@@ -2722,10 +2768,15 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
     if (wv == 0) {
         // ---- D: pod i's winner from the precomputed keys (la_resolve4_block's wave D) -----------
         uint32_t nd = 0, didx = 0xFFFFFFFFu;
+        // R32: the slot's node as the key's low half, k32_low(node); it changes only when a slot is
+        // created and at the window boundary, where didx is rebuilt from it
+        uint32_t dlow = 0;
         bool won = false;  // slot won a pod of the current window (it stays a slot in the next one)
         for (uint32_t w = 0; w < nwin; ++w) {
             const uint32_t s0 = w * K, kend = min(K, P - s0);
             const uint32_t knext = w + 1 < nwin ? min(K, P - s0 - K) : 0u;
+            uint32_t res_k32 = 0;  // R32: this lane's pod result, expanded after the window's last step
+            ResPub32 pv32 = none32;
             // next window's pod records (to LDS at the end; loaded unconditionally, clamped, so the
             // loads stay in flight through the window instead of being waited for at a branch join)
             // (three named registers, not an int4[PQ] array: the array stayed a private-memory
@@ -2745,117 +2796,168 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             if (w > 0) bmark(3);
             if (rdiag && lane == 0) store_coh_u64(&rdiag[15], __builtin_amdgcn_s_memrealtime());
             for (uint32_t i = 0; i < kend; ++i) {
-                QS_RSTAMP_BEGIN()
-                const int par = i & 1, pp = par ^ 1;
-                const uint64_t a = keyA[pp][lane], b = keyB[pp][lane], cl = keyC[pp][lane];
-                const uint64_t e1 = C1[pp][lane];
-                uint32_t fcl = 0;
-                NormInfo nf{0, 0, 0, 0};
-                if (NORM) {
-                    fcl = flagC[pp][lane];
-                    nf = wnorm2[w & 1][i];
-                }
-                const bool pnew = pv.ks != 0 && pv.slot < 0;
-                uint64_t sc = (lane == pv.slot) ? b : a;
-                uint32_t fl = 0;  // NORM: lost-holder flags of this slot (bit 0 taint, bit 1 affinity)
-                if (NORM) {
-                    fl = (uint32_t)sc & 3u;
-                    sc &= ~3ull;
-                }
-                uint64_t fk = ((uint32_t)lane < nd && sc) ? (sc | (uint64_t)(0xFFFFFFFFu - didx)) : 0ull;
-                // the new slot's key, read unconditionally (under a branch the compiler sank the
-                // keyC load into it: a second, dependent LDS round trip on D's chain)
-                const int srcl = pv.src >= 0 ? pv.src : 0;
-                const uint64_t cw = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(cl >> 32), srcl) << 32) |
-                                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cl, srcl);
-                if (pnew && (uint32_t)lane == pv.nd_old) fk = cw;
-                bool unsafe = false;
-                if (NORM) {
-                    const uint32_t fc = (uint32_t)__builtin_amdgcn_readlane((int)fcl, srcl);
-                    if (pnew && (uint32_t)lane == pv.nd_old) fl = fc;
-                    // do the selection-time maxima still hold for pod i?  A maximum is lost only
-                    // when every node attaining it is dirty and infeasible now
-                    if (F & kFeatTaint)
-                        unsafe |= nf.mt > 0 && (uint32_t)__popcll(__ballot((uint32_t)lane < nd && (fl & 1u))) >= nf.ct;
-                    if (F & kFeatAffinity)
-                        unsafe |= nf.ma > 0 && (uint32_t)__popcll(__ballot((uint32_t)lane < nd && (fl & 2u))) >= nf.ca;
-                }
-                if (NORM && unsafe) {
-                    if (lane == 0) pub[par] = ResPub{0, 0xFFFFFFFFu, -2, -1, nd, {0, 0}};  // STOP
-                } else {
-                    const uint64_t cand = (pv.ks != 0 && e1 != 0 && key_node(e1) == pv.w) ? 0ull : e1;
-                    const uint64_t best = fk > cand ? fk : cand;
-                    uint64_t ks;
-                    if (K32) {  // (score+1) < 2^10 and n <= 2^22: one 32-bit reduction
-                        const uint32_t tv = (uint32_t)(best >> 32);
-                        const uint32_t k32 = tv ? (tv << 22) | (0x3FFFFFu - key_node(best)) : 0u;
-                        const uint32_t m = wave_max_u32_dpp(k32);
-                        ks = m ? (((uint64_t)(m >> 22) << 32) | (uint64_t)(0xFFFFFFFFu - (0x3FFFFFu - (m & 0x3FFFFFu)))) : 0ull;
-                    } else {
-                        ks = wave_max_u64(best);
-                    }
-                    ResPub np{ks, ks ? key_node(ks) : 0xFFFFFFFFu, -1, -1, nd, {0, 0}};
-                    if (ks) {
-                        const uint64_t own = __ballot((uint32_t)lane < nd && didx == np.w);
+                if constexpr (R32) {
+                    // 32-bit keys end to end: A / B hand over score halves, the slot's node half
+                    // (dlow) is or-ed in, the maximum itself names the owner and the source lane
+                    QS_RSTAMP_BEGIN()
+                    const int par = i & 1, pp = par ^ 1;
+                    const uint32_t a = keyA[pp][lane], b = keyB[pp][lane], cl = keyC[pp][lane];
+                    const uint32_t e1 = C1[pp][lane];
+                    const bool pnew = pv32.k != 0u && pv32.slot < 0;
+                    const uint32_t sc = (lane == pv32.slot) ? b : a;
+                    uint32_t fk = ((uint32_t)lane < nd && sc) ? (sc | dlow) : 0u;
+                    // the new slot's key, read unconditionally (see the 64-bit form below)
+                    const int srcl = pv32.src >= 0 ? pv32.src : 0;
+                    const uint32_t cw = (uint32_t)__builtin_amdgcn_readlane((int)cl, srcl);
+                    if (pnew && (uint32_t)lane == pv32.nd_old) fk = cw;
+                    // a candidate taken by pod i-1's winner: the same node half
+                    const uint32_t cand = (pv32.k != 0u && ((e1 ^ pv32.k) & kK32NodeMask) == 0u) ? 0u : e1;
+                    const uint32_t m = wave_max_u32_dpp(fk > cand ? fk : cand);
+                    ResPub32 np{m, -1, -1, nd};
+                    if (m) {
+                        const uint32_t mlow = m & kK32NodeMask;
+                        const uint64_t own = __ballot((uint32_t)lane < nd && dlow == mlow);
                         if (own) {
                             np.slot = (int32_t)__builtin_ctzll(own);
                             won |= lane == np.slot;
                         } else {
-                            np.src = (int32_t)__builtin_ctzll(__ballot(cand == ks));
-                            if ((uint32_t)lane == nd) { didx = np.w; won = true; }
+                            np.src = (int32_t)__builtin_ctzll(__ballot(cand == m));
+                            if ((uint32_t)lane == nd) { dlow = mlow; won = true; }
                             ++nd;
-                            if (lane == 0)  // dirty from now on: wave C's next dirty-word reads see it
-                                __hip_atomic_fetch_or(&dirty[np.w >> 5], 1u << (np.w & 31), __ATOMIC_RELAXED,
+                            if (lane == 0) {  // dirty from now on: wave C's next dirty-word reads see it
+                                const uint32_t wn = kK32NodeMask - mlow;
+                                __hip_atomic_fetch_or(&dirty[wn >> 5], 1u << (wn & 31), __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
                         }
                     }
-                    pv = np;
-                    if (lane == 0) pub[par] = np;
+                    pv32 = np;
+                    if (lane == 0) write_pub32(&pub32[par], np);
                     if ((uint32_t)lane == i) {
-                        res_key = ks;
+                        res_k32 = m;
                         if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
                     }
                     if (i == 0 && w > 0) bmark(4);
-                }
-                QS_RSTAMP_MARK(0)
-                QS_RSTAMP_END()
-                __syncthreads();
-                if (NORM && unsafe) {
-                    // the exact rescan of pod i (every wave), then pod i's result as usual; a new
-                    // slot takes source lane 0, whose staged row / key / flags wave C rewrites
-                    if ((uint32_t)lane < nd) sidx[lane] = didx;
-                    if (lane == 0) *snd = nd;
-                    const uint64_t ks = res_rescan_wait(red_k);
-                    ResPub np{ks, ks ? key_node(ks) : 0xFFFFFFFFu, -1, -1, nd, {0, 0}};
-                    if (ks) {
-                        const uint64_t own = __ballot((uint32_t)lane < nd && didx == np.w);
-                        if (own) {
-                            np.slot = (int32_t)__builtin_ctzll(own);
-                            won |= lane == np.slot;
+                    QS_RSTAMP_MARK(0)
+                    QS_RSTAMP_END()
+                    __syncthreads();
+                } else {
+                    QS_RSTAMP_BEGIN()
+                    const int par = i & 1, pp = par ^ 1;
+                    const uint64_t a = keyA[pp][lane], b = keyB[pp][lane], cl = keyC[pp][lane];
+                    const uint64_t e1 = C1[pp][lane];
+                    uint32_t fcl = 0;
+                    NormInfo nf{0, 0, 0, 0};
+                    if (NORM) {
+                        fcl = flagC[pp][lane];
+                        nf = wnorm2[w & 1][i];
+                    }
+                    const bool pnew = pv.ks != 0 && pv.slot < 0;
+                    uint64_t sc = (lane == pv.slot) ? b : a;
+                    uint32_t fl = 0;  // NORM: lost-holder flags of this slot (bit 0 taint, bit 1 affinity)
+                    if (NORM) {
+                        fl = (uint32_t)sc & 3u;
+                        sc &= ~3ull;
+                    }
+                    uint64_t fk = ((uint32_t)lane < nd && sc) ? (sc | (uint64_t)(0xFFFFFFFFu - didx)) : 0ull;
+                    // the new slot's key, read unconditionally (under a branch the compiler sank the
+                    // keyC load into it: a second, dependent LDS round trip on D's chain)
+                    const int srcl = pv.src >= 0 ? pv.src : 0;
+                    const uint64_t cw = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(cl >> 32), srcl) << 32) |
+                                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cl, srcl);
+                    if (pnew && (uint32_t)lane == pv.nd_old) fk = cw;
+                    bool unsafe = false;
+                    if (NORM) {
+                        const uint32_t fc = (uint32_t)__builtin_amdgcn_readlane((int)fcl, srcl);
+                        if (pnew && (uint32_t)lane == pv.nd_old) fl = fc;
+                        // do the selection-time maxima still hold for pod i?  A maximum is lost only
+                        // when every node attaining it is dirty and infeasible now
+                        if (F & kFeatTaint)
+                            unsafe |= nf.mt > 0 && (uint32_t)__popcll(__ballot((uint32_t)lane < nd && (fl & 1u))) >= nf.ct;
+                        if (F & kFeatAffinity)
+                            unsafe |= nf.ma > 0 && (uint32_t)__popcll(__ballot((uint32_t)lane < nd && (fl & 2u))) >= nf.ca;
+                    }
+                    if (NORM && unsafe) {
+                        if (lane == 0) pub[par] = ResPub{0, 0xFFFFFFFFu, -2, -1, nd, {0, 0}};  // STOP
+                    } else {
+                        const uint64_t cand = (pv.ks != 0 && e1 != 0 && key_node(e1) == pv.w) ? 0ull : e1;
+                        const uint64_t best = fk > cand ? fk : cand;
+                        uint64_t ks;
+                        if (K32) {  // (score+1) < 2^10 and n <= 2^22: one 32-bit reduction
+                            const uint32_t tv = (uint32_t)(best >> 32);
+                            const uint32_t k32 = tv ? (tv << 22) | (0x3FFFFFu - key_node(best)) : 0u;
+                            const uint32_t m = wave_max_u32_dpp(k32);
+                            ks = m ? (((uint64_t)(m >> 22) << 32) | (uint64_t)(0xFFFFFFFFu - (0x3FFFFFu - (m & 0x3FFFFFu)))) : 0ull;
                         } else {
-                            np.src = 0;
-                            if ((uint32_t)lane == nd) { didx = np.w; won = true; }
-                            ++nd;
-                            if (lane == 0)
-                                __hip_atomic_fetch_or(&dirty[np.w >> 5], 1u << (np.w & 31), __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_WORKGROUP);
+                            ks = wave_max_u64(best);
                         }
+                        ResPub np{ks, ks ? key_node(ks) : 0xFFFFFFFFu, -1, -1, nd, {0, 0}};
+                        if (ks) {
+                            const uint64_t own = __ballot((uint32_t)lane < nd && didx == np.w);
+                            if (own) {
+                                np.slot = (int32_t)__builtin_ctzll(own);
+                                won |= lane == np.slot;
+                            } else {
+                                np.src = (int32_t)__builtin_ctzll(__ballot(cand == ks));
+                                if ((uint32_t)lane == nd) { didx = np.w; won = true; }
+                                ++nd;
+                                if (lane == 0)  // dirty from now on: wave C's next dirty-word reads see it
+                                    __hip_atomic_fetch_or(&dirty[np.w >> 5], 1u << (np.w & 31), __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
+                        }
+                        pv = np;
+                        if (lane == 0) pub[par] = np;
+                        if ((uint32_t)lane == i) {
+                            res_key = ks;
+                            if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
+                        }
+                        if (i == 0 && w > 0) bmark(4);
                     }
-                    pv = np;
-                    if (lane == 0) {
-                        pub[par] = np;
-                        if (nfall) atomicAdd(nfall, 1ull);  // pods resolved by an exact rescan
+                    QS_RSTAMP_MARK(0)
+                    QS_RSTAMP_END()
+                    __syncthreads();
+                    if (NORM && unsafe) {
+                        // the exact rescan of pod i (every wave), then pod i's result as usual; a new
+                        // slot takes source lane 0, whose staged row / key / flags wave C rewrites
+                        if ((uint32_t)lane < nd) sidx[lane] = didx;
+                        if (lane == 0) *snd = nd;
+                        const uint64_t ks = res_rescan_wait(red_k);
+                        ResPub np{ks, ks ? key_node(ks) : 0xFFFFFFFFu, -1, -1, nd, {0, 0}};
+                        if (ks) {
+                            const uint64_t own = __ballot((uint32_t)lane < nd && didx == np.w);
+                            if (own) {
+                                np.slot = (int32_t)__builtin_ctzll(own);
+                                won |= lane == np.slot;
+                            } else {
+                                np.src = 0;
+                                if ((uint32_t)lane == nd) { didx = np.w; won = true; }
+                                ++nd;
+                                if (lane == 0)
+                                    __hip_atomic_fetch_or(&dirty[np.w >> 5], 1u << (np.w & 31), __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
+                        }
+                        pv = np;
+                        if (lane == 0) {
+                            pub[par] = np;
+                            if (nfall) atomicAdd(nfall, 1ull);  // pods resolved by an exact rescan
+                        }
+                        if ((uint32_t)lane == i) {
+                            res_key = ks;
+                            if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
+                        }
+                        stopped = true;
+                        __syncthreads();  // R5
                     }
-                    if ((uint32_t)lane == i) {
-                        res_key = ks;
-                        if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
-                    }
-                    stopped = true;
-                    __syncthreads();  // R5
                 }
             }
             steps_ += kend;
             bmark(-1);
+            if constexpr (R32) {  // off the step chain: the 64-bit key and the slot nodes once per window
+                res_key = k32_to_key(res_k32);
+                didx = kK32NodeMask - dlow;
+            }
             if (NORM && stopped && lane == 0 && nfall) atomicAdd(nfall + 1, 1ull);  // windows with a rescan
             if ((uint32_t)lane < kend) {
                 out_node[s0 + lane] = res_key ? (int32_t)key_node(res_key) : -1;
@@ -2891,11 +2993,18 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             bmark(2);
             nd = (uint32_t)__popcll(wm);
             didx = (uint32_t)lane < nd ? dnode[lane] : 0xFFFFFFFFu;
+            dlow = k32_low(didx);  // (lanes >= nd: never compared)
             won = false;
-            if (lane == 0) pub[1] = none;
+            if (lane == 0) {
+                if constexpr (R32) write_pub32(&pub32[1], none32);
+                else pub[1] = none;
+            }
         }
     } else if (wv <= 2) {
         // ---- A / B: slot rows; apply pod i-1's winner, then the next pod's keys -----------------
+        // (the whole role as a generic lambda: FA picks the scorers once, before the loops)
+        auto role_ab = [&](auto fa) {
+        constexpr bool FA = decltype(fa)::value;
         RowT<F> S = empty_row<F>();
         RowX SX{};
         uint32_t nd = 0;
@@ -2907,7 +3016,8 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             double2 yr;
         };
         // NORM: st = the slot's static_raw against pod q (Tcur, or stS for a slot created this step)
-        auto slot_key = [&](const RowT<F> &r, const RowX &x, const PodT<F> &q, const PodN &pn, uint32_t st) -> uint64_t {
+        // (R32: the score half of a k32 alone, one 32-bit LDS write; D ors the slot's node in)
+        auto slot_key = [&](const RowT<F> &r, const RowX &x, const PodT<F> &q, const PodN &pn, uint32_t st) -> KT {
             const bool act = (uint32_t)lane < nd;
             if constexpr (QS_EXP_NORM_AB(NORM)) {
                 const bool f = fits<F>(r, x, q) && (st & 1u) != 0u;
@@ -2918,8 +3028,21 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             }
             QS_EXP_SLOT_KEY(act, r, q)
             const bool f = feasible<F>(r, x, q, px);
-            const uint32_t tot = node_total<F>(r, x, q, px, cv, 0, 0.0, 0, 0.0, nullptr);
-            return (act && f) ? ((uint64_t)(tot + 1) << 32) : 0ull;
+            // (NORM reaches this only in the experimental plain-A/B build: node_total with its terms)
+            uint32_t tot;
+            if constexpr (NORM) tot = node_total<F>(r, x, q, px, cv, 0, 0.0, 0, 0.0, nullptr);
+            else tot = fit_bal_total<F, FA>(r, x, q, cv);
+            if constexpr (R32) return (act && f) ? k32_score(tot + 1) : 0u;
+            else return (act && f) ? ((uint64_t)(tot + 1) << 32) : 0ull;
+        };
+        // the published winner (R32: the 16-byte form; ks then only says "some node won")
+        auto rpub = [&](int q) -> ResPub {
+            if constexpr (R32) {
+                const ResPub32 v = read_pub32(&pub32[q]);
+                return ResPub{v.k, 0u, v.slot, v.src, v.nd_old, {0, 0}};
+            } else {
+                return read_pub(&pub[q]);
+            }
         };
         uint32_t snew = 0;  // NORM: the static of a slot created by the applied winner
         // (the new slot's row is read from LDS at pv.src: a per-lane readlane of the own-lane staged
@@ -2981,7 +3104,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             for (uint32_t i = 0; i < kend; ++i) {
                 QS_RSTAMP_BEGIN()
                 const int par = i & 1, pp = par ^ 1;
-                ResPub pv = read_pub(&pub[pp]);
+                ResPub pv = rpub(pp);
                 const PodT<F> pn1 = wp[i + 1];
                 const uint32_t tst = NORM ? Tcur[min(i + 1, kResNormK - 1) * kResTStride + lane] : 0u;
                 PodN pnn{};
@@ -2989,7 +3112,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 __builtin_amdgcn_sched_barrier(0);  // the LDS reads go out before the pub's wait
                 if (NORM && i > 0 && pv.slot == -2) {  // D stopped at pod i-1
                     rescan_ab(i - 1, w & 1);
-                    pv = read_pub(&pub[pp]);
+                    pv = rpub(pp);
                 }
                 const uint32_t nd0 = nd;
                 QS_RSTAMP_MARK(0)
@@ -3018,8 +3141,8 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 QS_RSTAMP_END()
                 __syncthreads();
             }
-            if (NORM && read_pub(&pub[(kend - 1) & 1]).slot == -2) rescan_ab(kend - 1, w & 1);
-            apply(read_pub(&pub[(kend - 1) & 1]), (kend - 1) & 1, pprev, s0 + kend - 1);
+            if (NORM && rpub((kend - 1) & 1).slot == -2) rescan_ab(kend - 1, w & 1);
+            apply(rpub((kend - 1) & 1), (kend - 1) & 1, pprev, s0 + kend - 1);
             __syncthreads();  // B2 (D's slot ranks and nodes)
             const uint32_t rk = xrank[lane];
             const bool keep = (uint32_t)lane < nd && rk != 0xFFFFFFFFu;
@@ -3056,6 +3179,13 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
         if (wv == 1 && pend) {
             drain_stores();
             if (lane == 0) __hip_atomic_store((gu32 *)&ctl->done, pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        };
+        if constexpr (kFastAllocClass) {
+            if (fast_alloc) role_ab(std::integral_constant<bool, true>{});
+            else role_ab(std::integral_constant<bool, false>{});
+        } else {
+            role_ab(std::integral_constant<bool, false>{});
         }
     } else if (NORM && wv == 3) {
         // ---- C: candidate rows, C keys, the next pod's best clean entry; next-window prefetch -----
@@ -3286,10 +3416,12 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
         // ringX (wave 5), so a step issues no global load: C's row no longer waits behind older
         // sc1 entry loads (vector loads complete in issue order).  A/B read a new slot's row from
         // ringR as well, so C stages nothing.
-        uint64_t c1 = 0;
+        auto role_c = [&](auto fa) {
+        constexpr bool FA = decltype(fa)::value;
+        KT c1 = 0;
         uint32_t nfallback = 0;
-        auto dirty_bit = [&](uint64_t e) -> bool {
-            const uint32_t nidx = e ? key_node(e) : 0u;
+        auto dirty_bit = [&](KT e) -> bool {
+            const uint32_t nidx = e ? knode(e) : 0u;
             return (dirty[nidx >> 5] >> (nidx & 31)) & 1u;
         };
         for (uint32_t w = 0; w < nwin; ++w) {
@@ -3308,7 +3440,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 for (uint32_t j = 0; j < 3; ++j)
                     e[j] = j < kend ? load_coh_u64(lists + (size_t)j * 64 + lane) : 0ull;
 #pragma unroll
-                for (uint32_t j = 0; j < 3; ++j) ringE[(s0 + j) % kResRing][lane] = e[j];
+                for (uint32_t j = 0; j < 3; ++j) ringE[(s0 + j) % kResRing][lane] = kconv(e[j]);
                 const uint32_t n0 = e[0] ? key_node(e[0]) : 0u;
                 ringR[s0 % kResRing][lane] = load_row<F>(t, n0);
                 if (F & kFeatExt) {
@@ -3317,8 +3449,8 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 }
             }
             // pod 0's candidates against the dirty set at the window start (the inherited slots)
-            const uint64_t e0 = ringE[s0 % kResRing][lane];
-            c1 = (e0 != 0 && !dirty_bit(e0)) ? e0 : 0ull;
+            const KT e0 = ringE[s0 % kResRing][lane];
+            c1 = (e0 != 0 && !dirty_bit(e0)) ? e0 : (KT)0;
             C1[1][lane] = c1;
             if (w > 0) bmark(0);
             __syncthreads();  // B1
@@ -3331,7 +3463,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 // i-1, wave D marks a new slot in the step that creates it), pod i's candidate row
                 // (c1's), pod i+1's record.  C never reads the published winner: a candidate taken
                 // by pod i-1's winner is masked by D, which then never names that lane as a source.
-                const uint64_t en = ringE[(g + 1) % kResRing][lane];
+                const KT en = ringE[(g + 1) % kResRing][lane];
                 const RowT<F> r1 = ringR[g % kResRing][lane];
                 RowX x1{};
                 if (F & kFeatExt) {
@@ -3339,7 +3471,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                     x1.ae0 = e.x; x1.re0 = e.y; x1.ae1 = e.z; x1.re1 = e.w;
                 }
                 const PodT<F> pn1 = wp[i + 1];
-                const uint32_t en_node = en ? key_node(en) : 0u;
+                const uint32_t en_node = en ? knode(en) : 0u;
                 const uint32_t dword = dirty[en_node >> 5];
                 QS_RSTAMP_MARK(0)
                 // keyC: candidate c1's row + pod i, scored for pod i+1 (needs no pub)
@@ -3347,13 +3479,15 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 RowX crx = x1;
                 reserve(cr, crx, pcur, +1);
                 const bool f = feasible<F>(cr, crx, pn1, px);
-                const uint32_t tot = node_total<F>(cr, crx, pn1, px, cv, 0, 0.0, 0, 0.0, nullptr);
+                const uint32_t tot = fit_bal_total<F, FA>(cr, crx, pn1, cv);
                 QS_EXP_CAND_KEY(f, tot, cr, pn1)
                 QS_RSTAMP_MARK(1)
                 if (i + 1 < kend) {
-                    keyC[par][lane] = (c1 != 0 && f) ? pack_key(tot + 1, key_node(c1)) : 0ull;
+                    // (R32: the candidate's node half is its entry's)
+                    if constexpr (R32) keyC[par][lane] = (c1 != 0 && f) ? (k32_score(tot + 1) | (c1 & kK32NodeMask)) : 0u;
+                    else keyC[par][lane] = (c1 != 0 && f) ? pack_key(tot + 1, key_node(c1)) : 0ull;
                     const bool dirt = ((dword >> (en_node & 31)) & 1u) != 0;
-                    c1 = (en != 0 && !dirt) ? en : 0ull;  // pod i+1 against the dirty set through pod i-1
+                    c1 = (en != 0 && !dirt) ? en : (KT)0;  // pod i+1 against the dirty set through pod i-1
                     C1[par][lane] = c1;
                 }
                 QS_RSTAMP_MARK(2)
@@ -3366,6 +3500,13 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             bmark(-1);
         }
         if (rdiag && lane == 0) { rdiag[4] = nfallback; rdiag[5] = 0; rdiag[6] = 0; }
+        };
+        if constexpr (kFastAllocClass) {
+            if (fast_alloc) role_c(std::integral_constant<bool, true>{});
+            else role_c(std::integral_constant<bool, false>{});
+        } else {
+            role_c(std::integral_constant<bool, false>{});
+        }
     } else if (!NORM && wv == 4) {
         // ---- wave 4 (RING): list entries three pods ahead.  Step i (stream pod g) writes E(g+2),
         // whose sc1 load it issued one step earlier (the wait sits at the loop's top, where the
@@ -3389,7 +3530,7 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             __syncthreads();  // B1
             for (uint32_t i = 0; i < kend; ++i) {
                 const uint32_t g = s0 + i;
-                if (!(skip && i == 0)) ringE[(g + 2) % kResRing][lane] = ein;
+                if (!(skip && i == 0)) ringE[(g + 2) % kResRing][lane] = kconv(ein);  // (R32: converted here)
                 if (i == ic) {
                     if (pfw) lt = !((uint32_t)__builtin_amdgcn_readfirstlane(rdyv) >= tnext);
                     if (lane == 0) *late = lt ? 1u : 0u;
@@ -3424,8 +3565,8 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 const uint32_t g = s0 + i;
                 const bool go = i + 1 < kend || (pfw ? *late == 0u : !hasnext);
                 if (go) {
-                    const uint64_t e = ringE[(g + 1) % kResRing][lane];
-                    const uint32_t nd = e ? key_node(e) : 0u;
+                    const KT e = ringE[(g + 1) % kResRing][lane];
+                    const uint32_t nd = e ? knode(e) : 0u;
                     const RowT<F> r = load_row<F>(t, nd);
                     ringR[(g + 1) % kResRing][lane] = r;
                     if (F & kFeatExt) {
@@ -3641,7 +3782,7 @@ static hipError_t la_stream_res_f(const DevTable &t, const void *pods, const DPo
         return hipErrorInvalidValue;
     const uint32_t E2 = geo.e2;  // a pod's G*L <= 512 * E2 chunk keys, E2 per merging thread
     if (G * L > E2 * (uint32_t)kResBS || (E2 == 2 && (F & kFeatNorm))) return hipErrorInvalidValue;
-    const size_t lds4 = res_stream_lds_bytes<F>(t.n);
+    const size_t lds4 = res_stream_lds_bytes<F>(t.n, geo.k32 != 0);
     if (lds4 > kResLdsMax) return hipErrorInvalidValue;
     // NORM: K <= kResNormK staged records per window, and a task per workgroup (the G chunks of a
     // pod wait for each other's partial maxima)
@@ -3679,7 +3820,7 @@ constexpr size_t kResCtlBytes = sizeof(ResCtl);
 // CU (every workgroup of the launch carries the resolver's dynamic LDS); 0 if not instantiated.
 template <uint32_t F>
 static int la_stream_res_per_cu(const LaGeom &geo, uint32_t n) {
-    const size_t lds4 = res_stream_lds_bytes<F>(n);
+    const size_t lds4 = res_stream_lds_bytes<F>(n, geo.k32 != 0);
     const void *fn = nullptr;
 #define QS_RESP(EE, KK) \
     if (geo.E == EE && geo.e2 == 1 && (geo.k32 != 0) == KK) fn = (const void *)k_la_stream_res<F, EE, 1, KK>;

@@ -190,7 +190,10 @@ typedef struct qs_stats {
                                        the device table; the next call rebuilds it from the mirror) */
     int32_t resident;               /* 1: LOOKAHEAD ran as one resident launch (resolver + selector
                                        workgroups, k_la_stream_res); 0: per-window launches */
-    int32_t reserved;
+    int32_t resident_path;          /* resident launch only, else 0: bit 0 the resolver ran with 32-bit
+                                       keys end to end (ring form; QS_RES_K32=0 clears it), bit 1 its key
+                                       waves ran without the zero-allocatable terms (no node with
+                                       allocatable cpu or memory 0; QS_FAST_ALLOC=0 clears it) */
     /* per-kernel device time (config.profile_kernels = 1; HIP events on the library's stream):
      * [0] persistent, [1] scan (all per-pod kernels), [2] lookahead select, [3] lookahead resolve
      * (a resident stream is one launch, counted under [3]) */
