@@ -104,6 +104,7 @@ struct qs_stream {
     uint64_t epoch_after = 0;  // the context's table epoch right after the last run (FitError replay)
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
+    qs_ctx *owner = nullptr;  // the context that lists this stream (qs_ctx::streams); nullptr once it closed
     // LOOKAHEAD window sequence as an instantiated HIP graph, valid while gkey matches
     hipGraphExec_t gexec = nullptr;
     std::vector<uint8_t> gkey;
@@ -127,6 +128,11 @@ struct qs_ctx {
     uint32_t zero_alloc = 0;  // nodes of the mirror with allocatable cpu or memory 0 (DevCfg::all_alloc)
     qs::DevTable dt{};
     qs::DevCfg dc{};
+    // NodeResourcesFit scoring strategy (qs_set_scoring_strategy; spec S5 "Scoring strategies"): the
+    // type, its 128-byte device table (DevCfg::strat_tab()) and the prepared streams that pin it
+    int32_t strat = 0;
+    qs_host::DevBuf strat_tab;
+    std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes
     bool soa_valid = false;  // SoA copy matches the rows (engines that update rows only clear it)

@@ -75,7 +75,11 @@ struct DevTable {
 // kFeatRes selects the configurable scoring-resource form of LeastAllocated / BalancedAllocation
 // (spec S5 "Scoring resources": extended resources in the lists, lists other than {cpu, memory});
 // the host sets it with kFeatExt.
-enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u };
+// kFeatStrat selects the MostAllocated / RequestedToCapacityRatio form of the NodeResourcesFit
+// scorer (spec S5 "Scoring strategies"; which of the two: DevCfg::strat_tab); the host sets it with
+// kFeatRes | kFeatExt.
+enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u,
+                           kFeatStrat = 32u };
 
 // pod flags: bits 0-1 QoS, 4-6 required terms, 8-10 preferred terms, 12-13 anti-affinity kind,
 // 16-25 app group (spec S11)
@@ -101,6 +105,7 @@ struct DevCfg {
     // (1 cpu, 2 memory, 3 ext0, 4 ext1; 0 ends the list)
     int32_t we0, we1;
     uint32_t bal;
+    uint32_t strat_tab_lo;  // (see strat_tab() below)
     // Overlapped lookahead windows: the resolver of window w waits in-kernel for
     // ready >= (epoch << 32 | w + 1), published by k_ready_set after window w's select chain,
     // instead of a cross-stream event per window.  nullptr: no wait (the launch is ordered).
@@ -111,6 +116,7 @@ struct DevCfg {
     // the resident stream never deliver window 3's first task, so the resolver's wait times out
     // and the in-kernel werr drain runs for real.  0 in every normal run.
     uint32_t inject;
+    uint32_t strat_tab_hi;
     // Bound (s_memrealtime ticks, 100 MHz) of the resident stream's waits in its first window, whose
     // producers may be a peer rank still in host-side prepare (sharded: 5 s, as the per-window
     // mailbox wait, qs_dist.cpp); 0 = the 0.5 s bound of every later wait.
@@ -123,7 +129,17 @@ struct DevCfg {
     // the loops whose two-resource scorers skip the zero-allocatable selects (fit_bal_total<F, true>).
     // 0 runs the generic code.
     uint32_t all_alloc;
+    // kFeatStrat only: the shape function of RequestedToCapacityRatio as a device table of 128 bytes,
+    // entry p = raw(p) scaled to 0..100 for the utilisation p in 0..100 (qs_shape_table), written once
+    // before any launch that reads it; nullptr = MostAllocated (raw is the identity, nothing is
+    // looked up).  The pointer's halves sit in strat_tab_lo / strat_tab_hi above, the two words that
+    // were padding, so the record's size and every other member's kernel-argument offset stay as
+    // they were and the LeastAllocated kernels compile to the code they compiled to before.
+    __host__ __device__ const uint8_t *strat_tab() const {
+        return reinterpret_cast<const uint8_t *>(((uint64_t)strat_tab_hi << 32) | strat_tab_lo);
+    }
 };
+static_assert(sizeof(DevCfg) == 112, "DevCfg is a kernel argument of every scoring kernel: keep its layout");
 
 // Resolver prologue: thread 0 spins (s_sleep) until window s0/K's lists are published, then every
 // thread proceeds.  Bounded: after 0.5 s (s_memrealtime, 100 MHz) it records a timeout; once one is
@@ -552,6 +568,27 @@ __device__ __forceinline__ double fraction_w(double a, double r, double y) {
     return r >= a ? 1.0 : q;
 }
 
+// Utilisation of one resource for MostAllocated / RequestedToCapacityRatio (UP most_allocated.go#
+// mostRequestedScore, requested_to_capacity_ratio.go#buildRequestedToCapacityRatioScorerFunction):
+// floor(min(reqd, a) * 100 / a), which is 100 where reqd > a (v1.32 clips; RTCR evaluates raw(100)
+// there), 0 where a == 0 (ya == 0; the caller gives such a resource no weight).  floor_div's
+// preconditions hold: n = min(reqd, a) * 100 < 2^31 (a < 2^24) and the quotient is at most 100.
+__device__ __forceinline__ uint32_t utilization(int32_t a, int32_t reqd, double ya) {
+    const int32_t rq = reqd < a ? reqd : a;
+    return floor_div(__umul24((uint32_t)rq, 100u), ya);
+}
+// Wide layout: the remainder-corrected quotient of least_requested_w on n = min(reqd, a) * 100
+// (exact below 2^53; n * RN(1/a) within 100 * 2^-52 of n / a, the fma remainder exact).
+__device__ __forceinline__ uint32_t utilization_w(double a, double reqd, double ya) {
+    const double rq = reqd < a ? reqd : a;
+    const double n = rq * 100.0;
+    double q = __builtin_trunc(n * ya);
+    const double r = __builtin_fma(-q, a, n);
+    q = r < 0.0 ? q - 1.0 : q;
+    q = (r >= a && a > 0.0) ? q + 1.0 : q;
+    return (uint32_t)q;
+}
+
 // ---- spec S5/S6: QoS-weighted total of one feasible node ------------------------------------
 // floor(num / den) of a weighted mean of scores 0..100 (num = sum of score x weight < 2^24, den = the
 // weight sum < 2^18, num / den <= 100): the f32 estimate is within 100 * 2^-22 < 1 of num / den, so it
@@ -609,6 +646,35 @@ __device__ __forceinline__ ExtTerms ext_terms(const RowX &x, const P &p) {
 template <uint32_t F, bool FA = false, class R, class P>
 __device__ __forceinline__ uint32_t la_score(const R &r, const RowX &x, const P &p, const DevCfg &c) {
     const bool hc = r.ac != 0, hm = r.am != 0;
+    if constexpr ((F & kFeatStrat) != 0) {
+        // MostAllocated / RequestedToCapacityRatio over the configured list (spec S5 "Scoring
+        // strategies"): per entry the utilisation 0..100 of (alloc, reqd) as LeastAllocated pairs
+        // them; an entry with alloc == 0 (or an extended resource the pod does not request) is not
+        // counted.  The strategy is a kernel argument (wave-uniform: a table means
+        // RequestedToCapacityRatio): one scalar branch picks the form.
+        const ExtTerms e = ext_terms(x, p);
+        uint32_t uc = utilization(r.ac, r.zc + p.zc, r.yc), um;
+        if constexpr (std::is_same<R, RowW>::value) um = utilization_w(r.am, r.zm + p.zm, r.ym);
+        else um = utilization(r.am, r.zm + p.zm, r.ym);
+        uint32_t u0 = utilization(x.ae0, x.re0 + p.re0, e.y0), u1 = utilization(x.ae1, x.re1 + p.re1, e.y1);
+        uint32_t wce = hc ? (uint32_t)c.wc : 0u, wme = hm ? (uint32_t)c.wm : 0u;
+        uint32_t w0 = e.h0 ? (uint32_t)c.we0 : 0u, w1 = e.h1 ? (uint32_t)c.we1 : 0u;
+        const uint8_t *tb = c.strat_tab();
+        if (tb != nullptr) {
+            // raw(p) from the 101-entry table (indices are 0..100 by construction; the min keeps a
+            // read inside the 128-byte buffer whatever the row holds); four independent byte loads,
+            // issued together.  A resource whose score is 0 does not count towards the weight sum.
+            uc = tb[uc < 100u ? uc : 100u]; um = tb[um < 100u ? um : 100u];
+            u0 = tb[u0 < 100u ? u0 : 100u]; u1 = tb[u1 < 100u ? u1 : 100u];
+            wce = uc ? wce : 0u; wme = um ? wme : 0u; w0 = u0 ? w0 : 0u; w1 = u1 ? w1 : 0u;
+            const uint32_t num = __umul24(uc, wce) + __umul24(um, wme) + __umul24(u0, w0) + __umul24(u1, w1);
+            const uint32_t den = wce + wme + w0 + w1;
+            // Go's math.Round(num / den) = floor((2 num + den) / (2 den)) here (spec S10)
+            return div_small(2u * num + den, 2u * den);
+        }
+        const uint32_t num = __umul24(uc, wce) + __umul24(um, wme) + __umul24(u0, w0) + __umul24(u1, w1);
+        return div_small(num, wce + wme + w0 + w1);
+    }
     const uint32_t sc_c = least_requested(r.ac, r.zc + p.zc, r.yc);
     uint32_t sc_m;
     if constexpr (std::is_same<R, RowW>::value) sc_m = least_requested_w(r.am, r.zm + p.zm, r.ym);

@@ -111,6 +111,10 @@ uint32_t balanced_ids(const qs_config &c) {
 // (its two-fraction std is symmetric in the order).  Extended resources drop out of both lists when
 // no pod of the stream requests them (a scalar resource with podRequest == 0 is skipped).
 uint32_t res_feat(const qs_config &c, bool has_ext) {
+    // QS_FORCE_RES=1 (measurements, tools/strategy_compare.py): never reduce, so that
+    // LeastAllocated runs the kernel family the other strategies run, on the same lists.  Read once.
+    static const bool force = getenv("QS_FORCE_RES") && getenv("QS_FORCE_RES")[0] == '1';
+    if (force) return kFeatRes | kFeatExt;
     int64_t w[5];
     fit_weights(c, w);
     bool generic = has_ext && (w[QS_RES_EXT0] != 0 || w[QS_RES_EXT1] != 0);
@@ -122,6 +126,11 @@ uint32_t res_feat(const qs_config &c, bool has_ext) {
     }
     generic |= set != ((1u << QS_RES_CPU) | (1u << QS_RES_MEMORY));
     return generic ? (kFeatRes | kFeatExt) : 0u;
+}
+// MostAllocated / RequestedToCapacityRatio run the kFeatStrat kernels whatever the lists are: such a
+// stream (or pod) never reduces to the default two-resource kernels, which compute LeastAllocated.
+uint32_t strat_feat(const qs_ctx *c) {
+    return c->strat != QS_STRATEGY_LEAST_ALLOCATED ? (kFeatStrat | kFeatRes | kFeatExt) : 0u;
 }
 
 DevCfg make_devcfg(const qs_config &c) {
@@ -730,6 +739,8 @@ void percentile_stats(const std::vector<uint64_t> &st, qs_stats *s) {
 uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, int32_t *on, uint64_t *ok,
                      KernelTimer &kt) {
     const uint32_t n = c->m.n, P = s->p;
+    if (c->dc.feat & kFeatStrat)
+        fail(QS_EINVAL, "QS_MODE_BATCHED scores LeastAllocated only (qs_set_scoring_strategy)");
     if (c->dc.feat & (kFeatTaint | kFeatAffinity))
         fail(QS_EINVAL, "QS_MODE_BATCHED supports the Fit + Balanced (+ extended resources) profile");
     if (!c->dt.apps) fail(QS_EINVAL, "QS_MODE_BATCHED keeps anti-affinity state for tables up to 2^20 nodes");
@@ -883,6 +894,10 @@ qs_status qs_close(qs_ctx *c) {
         for (void *p : c->mbox_opened) (void)hipIpcCloseMemHandle(p);
         c->mbox_opened.clear();
         mbox_host_release(c);
+        // streams still prepared outlive the context: they keep their own buffers and are freed later
+        // by qs_stream_free, which must not reach for this context then
+        for (qs_stream *ps : c->streams) ps->owner = nullptr;
+        c->streams.clear();
     }
     hipStream_t s = c->stream, s2 = c->stream2;
     if (s2) (void)hipStreamSynchronize(s2);
@@ -891,6 +906,68 @@ qs_status qs_close(qs_ctx *c) {
     if (s) (void)hipStreamDestroy(s);
     if (s2) (void)hipStreamDestroy(s2);
     return QS_OK;
+}
+
+// The shape function as a table (UP helper/shape_score.go#BuildBrokenLinearFunction over scores scaled
+// by 10): throws QS_EINVAL with the reason for a bad shape.
+static void shape_table(const qs_shape_point *sh, uint32_t n, uint8_t table[101]) {
+    if (!sh || !table) fail(QS_EINVAL, "shape: null pointer");
+    if (n < 1 || n > QS_MAX_SHAPE) fail(QS_EINVAL, "shape: 1 to 16 points");
+    for (uint32_t i = 0; i < n; i++) {
+        if (sh[i].utilization < 0 || sh[i].utilization > 100) fail(QS_EINVAL, "shape: utilization must be in [0, 100]");
+        if (sh[i].score < 0 || sh[i].score > 10) fail(QS_EINVAL, "shape: score must be in [0, 10]");
+        if (i && sh[i].utilization <= sh[i - 1].utilization)
+            fail(QS_EINVAL, "shape: utilization must be strictly increasing");
+    }
+    for (int64_t p = 0; p <= 100; p++) {
+        int64_t v = (int64_t)sh[n - 1].score * 10;
+        for (uint32_t i = 0; i < n; i++) {
+            if (p > sh[i].utilization) continue;
+            const int64_t s1 = (int64_t)sh[i].score * 10;
+            if (i == 0) { v = s1; break; }
+            const int64_t s0 = (int64_t)sh[i - 1].score * 10, u0 = sh[i - 1].utilization, u1 = sh[i].utilization;
+            v = s0 + (s1 - s0) * (p - u0) / (u1 - u0);  // C++ integer division truncates, as Go's
+            break;
+        }
+        table[p] = (uint8_t)v;
+    }
+}
+
+qs_status qs_shape_table(const qs_shape_point *shape, uint32_t n, uint8_t table[101]) {
+    try {
+        shape_table(shape, n, table);
+    } catch (const QsError &) {
+        return QS_EINVAL;
+    }
+    return QS_OK;
+}
+
+qs_status qs_set_scoring_strategy(qs_ctx *c, const qs_scoring_strategy *s) {
+    return guarded(c, [&] {
+        if (!s) fail(QS_EINVAL, "null scoring strategy");
+        if (s->type != QS_STRATEGY_LEAST_ALLOCATED && s->type != QS_STRATEGY_MOST_ALLOCATED &&
+            s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO)
+            fail(QS_EINVAL, "unknown scoring strategy type");
+        if (s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO && s->n_shape != 0)
+            fail(QS_EINVAL, "a shape is given for a scoring strategy that takes none");
+        alignas(16) uint8_t tab[128] = {0};
+        if (s->type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO) {
+            if (s->n_shape < 1 || s->n_shape > QS_MAX_SHAPE) fail(QS_EINVAL, "shape: 1 to 16 points");
+            shape_table(s->shape, (uint32_t)s->n_shape, tab);
+        } else {
+            for (int p = 0; p <= 100; p++) tab[p] = (uint8_t)p;
+        }
+        if (!c->streams.empty()) fail(QS_ESTATE, "the scoring strategy cannot change while prepared streams exist");
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));  // no launch of this context still reads the table
+        c->strat_tab.ensure(sizeof tab);
+        HIPCHK(hipMemcpy(c->strat_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+        c->strat = s->type;
+        // DevCfg: a table means RequestedToCapacityRatio, none MostAllocated (kFeatStrat kernels only)
+        const uint64_t tp = s->type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO ? (uint64_t)(uintptr_t)c->strat_tab.p : 0;
+        c->dc.strat_tab_lo = (uint32_t)tp;
+        c->dc.strat_tab_hi = (uint32_t)(tp >> 32);
+    });
 }
 
 // (no context: why the calling thread's last qs_open / qs_open_shard failed, or "null context")
@@ -1234,7 +1311,7 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
     DevCfg dc = c->dc;
     const bool pod_ext = pod->req_ext[0] || pod->req_ext[1];
     dc.feat = feat_of(c->cfg) | (pod_ext ? kFeatExt : 0u) | (c->wide ? kFeatWide | kFeatExt : 0u) |
-              res_feat(c->cfg, pod_ext);
+              res_feat(c->cfg, pod_ext) | strat_feat(c);
     wts[2] = (dc.feat & kFeatTaint) ? (uint32_t)dc.wtt : 0u;
     wts[3] = (dc.feat & kFeatAffinity) ? (uint32_t)dc.wna : 0u;
     if (n == 0 || !c->dev_valid) {
@@ -1322,7 +1399,7 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         bool has_ext = false;
         for (uint32_t j = 0; j < p && !has_ext; j++) has_ext = pods[j].req_ext[0] || pods[j].req_ext[1];
         if (has_ext) s->feat |= kFeatExt;
-        s->feat |= res_feat(c->cfg, has_ext);
+        s->feat |= res_feat(c->cfg, has_ext) | strat_feat(c);
         s->order = qos_order(pods, p, c->cfg.qos_sort != 0);
         const size_t rb = pod_record_bytes(c->wide);
         std::vector<uint8_t> dp(rb * std::max<uint32_t>(p, 1));
@@ -1342,6 +1419,8 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         HIPCHK(hipMemcpyAsync(s->d_pods.p, dp.data(), rb * p, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(s->d_podx.p, dx.data(), sizeof(DPodX) * dx.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+        c->streams.push_back(s);  // (last: nothing after it throws)
+        s->owner = c;
     });
     if (st != QS_OK) {
         delete s;
@@ -1950,6 +2029,11 @@ qs_status qs_stream_results(qs_ctx *c, qs_stream *s, int32_t *placement, uint64_
 
 qs_status qs_stream_free(qs_ctx *c, qs_stream *s) {
     (void)c;
+    if (s && s->owner) {  // (nullptr: its context closed first, qs_close detached it)
+        std::lock_guard<std::mutex> lk(s->owner->mu);
+        auto &v = s->owner->streams;
+        v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    }
     delete s;
     return QS_OK;
 }
@@ -2023,6 +2107,7 @@ size_t qs_struct_size(int which) {
         case 3: return sizeof(qs_pod);
         case 4: return sizeof(qs_container);
         case 5: return sizeof(qs_stats);
+        case 6: return sizeof(qs_scoring_strategy);
         default: return 0;
     }
 }

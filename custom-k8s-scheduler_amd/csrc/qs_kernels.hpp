@@ -4346,6 +4346,9 @@ int wide_la_stream_res_per_cu(const LaGeom &geo, uint32_t feat, uint32_t n);
     int P##la_stream_res_per_cu(const LaGeom &geo, uint32_t feat, uint32_t n);
 QS_DECL_RES(res_compact_)
 QS_DECL_RES(res_wide_)
+// Scoring-strategy entry points (kFeatStrat; qs_kernels_strat.inc, the same shape)
+QS_DECL_RES(strat_compact_)
+QS_DECL_RES(strat_wide_)
 #undef QS_DECL_RES
 
 }  // namespace qs

@@ -31,6 +31,30 @@ int64_t least_requested_score(int64_t requested, int64_t capacity) {
     return ((capacity - requested) * kMaxNodeScore) / capacity;
 }
 
+// UP noderesources/most_allocated.go#mostRequestedScore (v1.32 clips an over-committed resource to
+// its capacity; it does not score it 0)
+int64_t most_requested_score(int64_t requested, int64_t capacity) {
+    if (capacity == 0) return 0;
+    if (requested > capacity) requested = capacity;
+    return (requested * kMaxNodeScore) / capacity;
+}
+
+// UP helper/shape_score.go#BuildBrokenLinearFunction over the shape's scores scaled by
+// MaxNodeScore / MaxCustomPriorityScore = 10 (requested_to_capacity_ratio.go); int64 division
+// truncates toward zero, as Go's
+int64_t broken_linear(const qs_scoring_strategy &st, int64_t p) {
+    const int n = st.n_shape;
+    for (int i = 0; i < n; ++i) {
+        if (p > st.shape[i].utilization) continue;
+        const int64_t s1 = (int64_t)st.shape[i].score * 10;
+        if (i == 0) return s1;
+        const int64_t s0 = (int64_t)st.shape[i - 1].score * 10;
+        const int64_t u0 = st.shape[i - 1].utilization, u1 = st.shape[i].utilization;
+        return s0 + (s1 - s0) * (p - u0) / (u1 - u0);
+    }
+    return n > 0 ? (int64_t)st.shape[n - 1].score * 10 : 0;
+}
+
 // UP helper/normalize_score.go#DefaultNormalizeScore
 void default_normalize(NodeScoreList &scores, bool reverse) {
     int64_t mx = 0;
@@ -95,10 +119,43 @@ std::pair<int64_t, int64_t> alloc_request(const NodeInfo &ni, const PodResources
     }
 }
 
+}  // namespace
+
+// The three scorers of NodeResourcesFit over (allocatable, requested, weight) entries, int64 / double
+// as upstream: LeastAllocated (UP least_allocated.go#leastResourceScorer), MostAllocated (UP
+// most_allocated.go#mostResourceScorer), RequestedToCapacityRatio (UP requested_to_capacity_ratio.go#
+// buildRequestedToCapacityRatioScorerFunction: a resource whose shape score is 0 does not count
+// towards the weight sum; math.Round of the float64 quotient).  Entries with allocatable 0 are skipped.
+int64_t FitStrategyScore(const qs_scoring_strategy &st, const int64_t *alloc, const int64_t *reqd,
+                         const int64_t *weight, int n) {
+    int64_t score = 0, wsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (alloc[i] == 0) continue;
+        if (st.type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO) {
+            const int64_t s = reqd[i] > alloc[i] ? broken_linear(st, 100)
+                                                 : broken_linear(st, reqd[i] * kMaxNodeScore / alloc[i]);
+            if (s > 0) {
+                score += s * weight[i];
+                wsum += weight[i];
+            }
+            continue;
+        }
+        score += (st.type == QS_STRATEGY_MOST_ALLOCATED ? most_requested_score(reqd[i], alloc[i])
+                                                        : least_requested_score(reqd[i], alloc[i])) * weight[i];
+        wsum += weight[i];
+    }
+    if (wsum == 0) return 0;
+    if (st.type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO) return (int64_t)std::round((double)score / (double)wsum);
+    return score / wsum;
+}
+
+namespace {
+
 // ---- NodeResourcesFit ------------------------------------------------------------------------
 class NodeResourcesFit final : public PreFilterPlugin, public FilterPlugin, public ScorePlugin {
    public:
-    NodeResourcesFit(const qs_config &cfg, Handle *h) : res_(fit_list(cfg)), h_(h) {}
+    NodeResourcesFit(const qs_config &cfg, const qs_scoring_strategy &st, Handle *h)
+        : res_(fit_list(cfg)), st_(st), h_(h) {}
     std::string Name() const override { return kNodeResourcesFit; }
 
     // UP fit.go#PreFilter computes the pod's requests once per cycle (preFilterState)
@@ -132,8 +189,9 @@ class NodeResourcesFit final : public PreFilterPlugin, public FilterPlugin, publ
         return why.empty() ? Status::OK() : Status(Code::Unschedulable, why);
     }
 
-    // LeastAllocated strategy over the scoring resources (UP least_allocated.go#leastResourceScorer,
-    // resource_allocation.go#score): requested = NonZeroRequested + the pod's non-zero requests for
+    // The configured strategy (LeastAllocated by default) over the scoring resources (UP
+    // least_allocated.go / most_allocated.go / requested_to_capacity_ratio.go, resource_allocation.go#
+    // score): requested = NonZeroRequested + the pod's non-zero requests for
     // cpu / memory, Requested + the request for extended resources; resources with allocatable 0 are
     // skipped (their weight not counted)
     std::pair<int64_t, Status> Score(CycleState &s, const Pod &pod, const std::string &node) override {
@@ -141,18 +199,21 @@ class NodeResourcesFit final : public PreFilterPlugin, public FilterPlugin, publ
         if (!ni) return {0, Status::AsError("node " + node + " not found")};
         PodResources tmp;
         const PodResources &r = resources_of(s, pod, h_, &tmp);
-        int64_t score = 0, wsum = 0;
+        int64_t alloc[QS_MAX_SCORE_RES], reqd[QS_MAX_SCORE_RES], weight[QS_MAX_SCORE_RES];
+        int n = 0;
         for (const auto &rw : res_) {
+            if (n == QS_MAX_SCORE_RES) break;
             const auto ar = alloc_request(*ni, r, rw.first, false, h_->ExtendedResourceNames());
-            if (ar.first == 0) continue;
-            score += least_requested_score(ar.second, ar.first) * rw.second;
-            wsum += rw.second;
+            alloc[n] = ar.first;
+            reqd[n] = ar.second;
+            weight[n++] = rw.second;
         }
-        return {wsum == 0 ? 0 : score / wsum, Status::OK()};
+        return {FitStrategyScore(st_, alloc, reqd, weight, n), Status::OK()};
     }
 
    private:
     ResList res_;
+    qs_scoring_strategy st_;
     Handle *h_;
 };
 
@@ -306,9 +367,11 @@ const char *kProfileName[3] = {"besteffort", "burstable", "guaranteed"};
 
 }  // namespace
 
-Registry CPURegistry(const qs_config &cfg) {
+Registry CPURegistry(const qs_config &cfg) { return CPURegistry(cfg, qs_scoring_strategy{}); }
+
+Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy &st) {
     Registry r;
-    r[kNodeResourcesFit] = [cfg](Handle *h) { return std::make_shared<NodeResourcesFit>(cfg, h); };
+    r[kNodeResourcesFit] = [cfg, st](Handle *h) { return std::make_shared<NodeResourcesFit>(cfg, st, h); };
     r[kNodeResourcesBalancedAllocation] = [cfg](Handle *h) { return std::make_shared<BalancedAllocation>(cfg, h); };
     r[kTaintToleration] = [](Handle *h) { return std::make_shared<TaintToleration>(h); };
     r[kNodeAffinity] = [](Handle *h) { return std::make_shared<NodeAffinity>(h); };

@@ -8,7 +8,9 @@
 //   NodeResourcesFit                  PreFilter / Filter (UP noderesources/fit.go#{PreFilter,Filter,
 //                                     fitsRequest}) and Score with the LeastAllocated strategy
 //                                     (UP noderesources/least_allocated.go#leastResourceScorer over
-//                                     NonZeroRequested, resource_allocation.go#score)
+//                                     NonZeroRequested, resource_allocation.go#score), or MostAllocated /
+//                                     RequestedToCapacityRatio (UP most_allocated.go,
+//                                     requested_to_capacity_ratio.go) when a strategy is given
 //   NodeResourcesBalancedAllocation   Score (UP noderesources/balanced_allocation.go#
 //                                     balancedResourceScorer over Requested, float64)
 //   TaintToleration                   Filter / Score / NormalizeScore reverse (UP tainttoleration/
@@ -37,6 +39,12 @@ inline const char *kCPUQoSSort = "QoSSort";
 // cfg: the scoring-resource lists (fit_resources / balanced_resources, or fit_weight_cpu / _mem and
 // [cpu, memory]; extended resource k = the handle's ExtendedResourceNames()[k]), balanced_skip_besteffort.
 Registry CPURegistry(const qs_config &cfg);
+// ... with NodeResourcesFitArgs.ScoringStrategy.Type (and the RequestedToCapacityRatio shape, assumed
+// valid: qs_shape_table checks one); the one-argument form scores LeastAllocated
+Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy &strategy);
+// The scorer itself over n (allocatable, requested, weight) entries (spec S5 "Scoring strategies")
+int64_t FitStrategyScore(const qs_scoring_strategy &strategy, const int64_t *alloc, const int64_t *reqd,
+                         const int64_t *weight, int n);
 // One profile per QoS class ("besteffort", "burstable", "guaranteed"): NodeResourcesFit weight
 // w_fit[q], NodeResourcesBalancedAllocation w_bal[q], TaintToleration w_taint / NodeAffinity
 // w_affinity when enabled.

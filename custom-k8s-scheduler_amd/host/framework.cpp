@@ -440,6 +440,7 @@ ScheduleResult Scheduler::ScheduleOne(const QueuedPodInfo &qp) {
         }
         for (size_t i = 1; i < total.size(); ++i)
             if (total[i] > total[pick]) pick = (int)i;  // ties keep the lower node index
+        res.total_score = total[pick];
     }
     const int ix = feasible_ix[pick];
     // assume, then Reserve (Unreserve + forget on failure)

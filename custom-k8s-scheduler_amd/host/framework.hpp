@@ -239,6 +239,8 @@ struct ScheduleResult {
     std::string suggested_host;  // empty: unschedulable / error
     int node_index = -1;
     int evaluated_nodes = 0, feasible_nodes = 0;
+    int64_t total_score = -1;    // the chosen node's weighted total (spec S6); -1 when the score pass did
+                                 // not run (one feasible node, as upstream, or none)
     Status status;
     std::string profile;
 };

@@ -14,6 +14,16 @@ GpuBackend::GpuBackend(const qs_config &cfg, int device) : cfg_(cfg) {
                                  "): libqsched needs an MI355X device; there is no CPU fallback");
 }
 
+GpuBackend::GpuBackend(const qs_config &cfg, const qs_scoring_strategy &strategy, int device)
+    : GpuBackend(cfg, device) {
+    if (qs_set_scoring_strategy(ctx_, &strategy) != QS_OK) {
+        const std::string why = err("qs_set_scoring_strategy");
+        qs_close(ctx_);  // (the destructor does not run when a constructor throws)
+        ctx_ = nullptr;
+        throw std::runtime_error(why);
+    }
+}
+
 GpuBackend::~GpuBackend() {
     if (ctx_) qs_close(ctx_);
 }

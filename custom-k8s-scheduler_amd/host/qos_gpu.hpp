@@ -45,6 +45,9 @@ class GpuBackend {
     // cfg: taint/affinity plugin switches and weights for the library's own `total`/`best`.
     // Throws std::runtime_error when libqsched cannot open the device (no CPU fallback).
     GpuBackend(const qs_config &cfg, int device = 0);
+    // ... with NodeResourcesFitArgs.ScoringStrategy.Type / the RequestedToCapacityRatio shape passed to
+    // the context (qs_set_scoring_strategy); a rejected strategy throws std::runtime_error with the reason.
+    GpuBackend(const qs_config &cfg, const qs_scoring_strategy &strategy, int device = 0);
     ~GpuBackend();
     GpuBackend(const GpuBackend &) = delete;
     GpuBackend &operator=(const GpuBackend &) = delete;

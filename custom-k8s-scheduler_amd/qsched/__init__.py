@@ -19,12 +19,12 @@ import numpy as np
 
 from ._abi import (ENGINES, ENGINE_NAMES, EXPORTED, LIB_PATH, POD_DTYPE, QS_ABI_VERSION,
                    QS_MAX_EXT, QS_MAX_SCORE_RES, QS_MAX_TERMS, QS_MODE_BATCHED, QS_MODE_EXACT, QS_OK,
-                   RESOURCES, FIT_REASONS, QS_FIT_TAINT, QschedError,
-                   QschedLibraryMissing, QsConfig, QsContainer, QsNodeRow, QsNodeSoa, QsStats,
-                   load)
+                   RESOURCES, FIT_REASONS, QS_FIT_TAINT, QS_MAX_SHAPE, STRATEGIES, QschedError,
+                   QschedLibraryMissing, QsConfig, QsContainer, QsNodeRow, QsNodeSoa, QsScoringStrategy,
+                   QsStats, load)
 
 __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_struct", "fit_error_message",
-           "synth_generate", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
+           "synth_generate", "shape_table", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
            "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH"]
 
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
@@ -129,7 +129,11 @@ class Scheduler:
         every rank loads the same full table and pod stream; RCCL exchanges the per-window lists.
         unique_id None: the peer-memory mailbox transport (mailbox_export / mailbox_connect)."""
         self.lib = load()
-        self.cfg = Config(config or {}).to_c()
+        config = dict(config or {})
+        # NodeResourcesFitArgs.ScoringStrategy.Type / RequestedToCapacityRatio.Shape are not part of
+        # qs_config: they are set on the open context (qs_set_scoring_strategy)
+        strategy, shape = config.pop("scoring_strategy", None), config.pop("shape", None)
+        self.cfg = Config(config).to_c()
         ctx = ctypes.c_void_p()
         if shard is None:
             st = self.lib.qs_open(ctypes.byref(self.cfg), device, ctypes.byref(ctx))
@@ -143,6 +147,25 @@ class Scheduler:
             raise QschedError(st, "qs_open failed: " + (why.decode() if why else "no HIP device?"))
         self.ctx = ctx
         self.n = 0
+        if strategy is not None or shape is not None:
+            try:
+                self.set_scoring_strategy(strategy or "LeastAllocated", shape)
+            except Exception:
+                self.close()
+                raise
+
+    def set_scoring_strategy(self, strategy, shape=None):
+        """qs_set_scoring_strategy: "LeastAllocated" | "MostAllocated" | "RequestedToCapacityRatio"
+        (or the qs_scoring_strategy_type id) and, for the last, shape = [(utilization, score), ...]."""
+        shape = list(shape or [])
+        if len(shape) > QS_MAX_SHAPE:
+            raise ValueError(f"at most {QS_MAX_SHAPE} shape points")
+        st = QsScoringStrategy()
+        st.type = STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
+        st.n_shape = len(shape)
+        for i, (u, sc) in enumerate(shape):
+            st.shape[i][0], st.shape[i][1] = int(u), int(sc)
+        self._chk(self.lib.qs_set_scoring_strategy(self.ctx, ctypes.byref(st)))
 
     def mailbox_export(self) -> bytes:
         """qs_dist_mailbox_export: this rank's 64-byte mailbox IPC handle (sharded contexts opened
@@ -328,6 +351,21 @@ def dist_unique_id() -> bytes:
     if st != QS_OK:
         raise QschedError(st, "qs_dist_unique_id failed")
     return bytes(buf)
+
+
+def shape_table(shape):
+    """qs_shape_table: the 101-entry table raw(0..100) (scores scaled to 0..100) of a
+    RequestedToCapacityRatio shape [(utilization, score), ...]; raises QschedError for a bad shape."""
+    lib = load()
+    shape = list(shape)
+    pts = ((ctypes.c_int32 * 2) * max(1, len(shape)))()
+    for i, (u, sc) in enumerate(shape):
+        pts[i][0], pts[i][1] = int(u), int(sc)
+    out = np.zeros(101, np.uint8)
+    st = lib.qs_shape_table(pts, len(shape), _ptr(out))
+    if st != QS_OK:
+        raise QschedError(st, "qs_shape_table: bad shape")
+    return out
 
 
 def synth_generate(config: int, n: int, p: int, seed=None):

@@ -31,6 +31,10 @@ QS_FIT_TAINT = 5
 # qs_resource: scoring-resource ids ("ext0" / "ext1" = the table's extended-resource columns)
 RESOURCES = {"cpu": 1, "memory": 2, "ext0": 3, "ext1": 4}
 
+# qs_scoring_strategy_type (NodeResourcesFitArgs.ScoringStrategy.Type)
+STRATEGIES = {"LeastAllocated": 0, "MostAllocated": 1, "RequestedToCapacityRatio": 2}
+QS_MAX_SHAPE = 16
+
 QS_OK, QS_EINVAL, QS_EDEVICE, QS_ETIMEOUT, QS_ENOMEM, QS_ESTATE = range(6)
 STATUS_NAMES = {0: "QS_OK", 1: "QS_EINVAL", 2: "QS_EDEVICE", 3: "QS_ETIMEOUT", 4: "QS_ENOMEM",
                 5: "QS_ESTATE"}
@@ -66,6 +70,11 @@ class QsConfig(ctypes.Structure):
                 ("n_balanced_resources", ctypes.c_int32),
                 ("balanced_resources", ctypes.c_int32 * QS_MAX_SCORE_RES),
                 ("reserved", ctypes.c_int32 * 3)]
+
+
+class QsScoringStrategy(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("n_shape", ctypes.c_int32),
+                ("shape", (ctypes.c_int32 * 2) * QS_MAX_SHAPE)]  # qs_shape_point {utilization, score}
 
 
 _NODE_COLS = ["alloc_cpu", "alloc_mem", "alloc_ext", "max_pods", "req_cpu", "req_mem", "req_ext",
@@ -137,6 +146,8 @@ _SIGS = {
     "qs_dist_unique_id": (ctypes.c_int, [_P]),
     "qs_dist_mailbox_export": (ctypes.c_int, [_P, _P]),
     "qs_dist_mailbox_connect": (ctypes.c_int, [_P, _P]),
+    "qs_set_scoring_strategy": (ctypes.c_int, [_P, _P]),
+    "qs_shape_table": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "qs_close": (ctypes.c_int, [_P]),
     "qs_last_error": (ctypes.c_char_p, [_P]),
     "qs_version": (ctypes.c_char_p, []),
@@ -182,7 +193,8 @@ def load(path: str = LIB_PATH):
         fn.restype = res
         fn.argtypes = args
     expect = {0: ctypes.sizeof(QsConfig), 1: ctypes.sizeof(QsNodeSoa), 2: ctypes.sizeof(QsNodeRow),
-              3: POD_DTYPE.itemsize, 4: ctypes.sizeof(QsContainer), 5: ctypes.sizeof(QsStats)}
+              3: POD_DTYPE.itemsize, 4: ctypes.sizeof(QsContainer), 5: ctypes.sizeof(QsStats),
+              6: ctypes.sizeof(QsScoringStrategy)}
     for k, v in expect.items():
         got = lib.qs_struct_size(k)
         if got != v:

@@ -9,6 +9,9 @@
  * beyond the north_star's "thin cgo C-ABI" in BASELINE.json:5):
  *   qs_open / qs_close        framework.Handle-scoped plugin state (UP cmd/kube-scheduler/app#WithPlugin
  *                             factory `func(ctx, runtime.Object, framework.Handle) (framework.Plugin, error)`)
+ *   qs_set_scoring_strategy   NodeResourcesFitArgs.ScoringStrategy.Type / RequestedToCapacityRatio.Shape
+ *                             (UP apis/config/types_pluginargs.go#ScoringStrategy; noderesources/fit.go#NewFit
+ *                             picks the scorer from nodeResourceStrategyTypeMap)
  *   qs_nodes_load             Cache.UpdateSnapshot → Snapshot NodeInfo list (UP backend/cache#Snapshot)
  *   qs_node_upsert            per-NodeInfo Generation diff (UP framework/types.go#NodeInfo.Generation)
  *   qs_score_pod              PreFilter+Filter+PreScore+Score+NormalizeScore for ALL nodes of one pod
@@ -74,6 +77,29 @@ typedef struct qs_resource_spec {
     int32_t resource; /* qs_resource */
     int32_t weight;   /* 1..100 (UP apis/config/validation#validateResources) */
 } qs_resource_spec;
+
+/* NodeResourcesFitArgs.ScoringStrategy.Type (UP apis/config/types_pluginargs.go#ScoringStrategyType;
+ * spec/semantics.md S5 "Scoring strategies"): LeastAllocated spreads (UP noderesources/
+ * least_allocated.go#leastResourceScorer), MostAllocated bin-packs (UP most_allocated.go#
+ * mostResourceScorer), RequestedToCapacityRatio scores each resource's utilisation through a
+ * piecewise-linear shape (UP requested_to_capacity_ratio.go#requestedToCapacityRatioScorer,
+ * helper/shape_score.go#BuildBrokenLinearFunction). */
+typedef enum qs_scoring_strategy_type {
+    QS_STRATEGY_LEAST_ALLOCATED = 0,
+    QS_STRATEGY_MOST_ALLOCATED = 1,
+    QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO = 2
+} qs_scoring_strategy_type;
+/* One point of RequestedToCapacityRatioParam.Shape (UP apis/config#UtilizationShapePoint):
+ * utilization 0..100 strictly increasing along the shape, score 0..10 (MaxCustomPriorityScore). */
+typedef struct qs_shape_point {
+    int32_t utilization, score;
+} qs_shape_point;
+#define QS_MAX_SHAPE 16
+typedef struct qs_scoring_strategy {
+    int32_t type;    /* qs_scoring_strategy_type */
+    int32_t n_shape; /* RequestedToCapacityRatio: 1..QS_MAX_SHAPE points; 0 for the other types */
+    qs_shape_point shape[QS_MAX_SHAPE];
+} qs_scoring_strategy;
 
 /* Which device engine runs the exact stream (all are bit-exact; AUTO picks the fastest). */
 typedef enum qs_engine {
@@ -232,6 +258,14 @@ QS_API qs_status qs_dist_unique_id(uint8_t out[128]);
  * Replaces (with qs_open_shard) the per-pod ncclAllReduce exchange of SURVEY.md §8(e). */
 QS_API qs_status qs_dist_mailbox_export(qs_ctx *ctx, uint8_t handle[64]);
 QS_API qs_status qs_dist_mailbox_connect(qs_ctx *ctx, const uint8_t *handles /* world x 64 bytes */);
+/* The scoring strategy of NodeResourcesFit for every later call on the context (qs_score_pod, streams
+ * prepared afterwards, every exact engine); a new context scores LeastAllocated.  The resources and
+ * weights stay those of qs_config (fit_resources, or fit_weight_cpu / fit_weight_mem); BalancedAllocation
+ * is untouched.  QS_ESTATE while the context holds prepared streams (free them first); QS_EINVAL for an
+ * unknown type, a bad shape (empty, more than QS_MAX_SHAPE points, utilization outside 0..100 or not
+ * strictly increasing, score outside 0..10), or a shape given for a type that takes none.
+ * QS_MODE_BATCHED runs LeastAllocated only: with another strategy set qs_stream_run returns QS_EINVAL. */
+QS_API qs_status qs_set_scoring_strategy(qs_ctx *ctx, const qs_scoring_strategy *s);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);
@@ -267,6 +301,7 @@ QS_API qs_status qs_schedule_stream(qs_ctx *ctx, const qs_pod *pods, uint32_t p,
 QS_API qs_status qs_stream_prepare(qs_ctx *ctx, const qs_pod *pods, uint32_t p, qs_stream **out);
 QS_API qs_status qs_stream_run(qs_ctx *ctx, qs_stream *s, qs_mode mode, qs_stats *stats);
 QS_API qs_status qs_stream_results(qs_ctx *ctx, qs_stream *s, int32_t *placement_p, uint64_t *best_key_p);
+/* Frees the stream (ctx may be NULL).  A stream may also be freed after its context was closed. */
 QS_API qs_status qs_stream_free(qs_ctx *ctx, qs_stream *s);
 /* Per-pod device timestamps (100 MHz s_memrealtime ticks, stream order; record_timestamps = 1). */
 QS_API qs_status qs_stream_stamps(qs_ctx *ctx, qs_stream *s, uint64_t *stamps_p);
@@ -306,8 +341,13 @@ QS_API qs_status qs_pod_from_containers(const qs_container *c, uint32_t nc, cons
                                  qs_pod *out);
 QS_API int32_t qs_compute_qos(const qs_container *c, uint32_t nc);
 /* sizeof of the ABI structs for binding self-checks: 0 config, 1 node_soa, 2 node_row, 3 pod,
- * 4 container, 5 stats. */
+ * 4 container, 5 stats, 6 scoring_strategy. */
 QS_API size_t qs_struct_size(int which);
+/* The shape function of RequestedToCapacityRatio as a table (no context): validates the shape as
+ * qs_set_scoring_strategy does and writes table[p] = raw(p) * 10 for the utilisation p = 0..100
+ * (UP helper/shape_score.go#BuildBrokenLinearFunction with Go's truncating integer division, scores
+ * scaled by MaxNodeScore / MaxCustomPriorityScore = 10).  QS_EINVAL for a bad shape or a null pointer. */
+QS_API qs_status qs_shape_table(const qs_shape_point *shape, uint32_t n, uint8_t table[101]);
 QS_API qs_status qs_synth_generate(int config, uint64_t seed, uint32_t n, uint32_t p,
                             const qs_node_soa_out *nodes, qs_pod *pods);
 
