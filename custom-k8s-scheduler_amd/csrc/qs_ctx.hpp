@@ -128,9 +128,11 @@ struct qs_ctx {
     uint32_t zero_alloc = 0;  // nodes of the mirror with allocatable cpu or memory 0 (DevCfg::all_alloc)
     qs::DevTable dt{};
     qs::DevCfg dc{};
-    // NodeResourcesFit scoring strategy (qs_set_scoring_strategy; spec S5 "Scoring strategies"): the
-    // type, its 128-byte device table (DevCfg::strat_tab()) and the prepared streams that pin it
-    int32_t strat = 0;
+    // NodeResourcesFit scoring strategy of each QoS class (qs_set_scoring_strategy[_qos]; spec S5
+    // "Scoring strategies", S9 "Strategy per QoS class"): what was set, the device tables (3 x 128
+    // bytes, class q at byte 128 q, zeros for a class that takes none; DevCfg::strat_tab() points at
+    // them while some class scores RequestedToCapacityRatio) and the prepared streams that pin them
+    qs_scoring_strategy strat[3] = {};
     qs_host::DevBuf strat_tab;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -75,14 +76,18 @@ struct DevTable {
 // kFeatRes selects the configurable scoring-resource form of LeastAllocated / BalancedAllocation
 // (spec S5 "Scoring resources": extended resources in the lists, lists other than {cpu, memory});
 // the host sets it with kFeatExt.
-// kFeatStrat selects the MostAllocated / RequestedToCapacityRatio form of the NodeResourcesFit
-// scorer (spec S5 "Scoring strategies"; which of the two: DevCfg::strat_tab); the host sets it with
-// kFeatRes | kFeatExt.
+// kFeatStrat selects the per-pod strategy form of the NodeResourcesFit scorer (spec S5 "Scoring
+// strategies", S9 "Strategy per QoS class": LeastAllocated, MostAllocated or RequestedToCapacityRatio
+// as the pod record says, pod_sid); the host sets it with kFeatRes | kFeatExt when some pod's class
+// has a strategy other than LeastAllocated.
 enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u,
                            kFeatStrat = 32u };
 
-// pod flags: bits 0-1 QoS, 4-6 required terms, 8-10 preferred terms, 12-13 anti-affinity kind,
+// pod flags: bits 0-1 QoS, 2-3 the NodeResourcesFit strategy of the pod's QoS class (0 Least, 1 Most,
+// 2 RequestedToCapacityRatio; read by the kFeatStrat scorer only, every other reader masks its own
+// field), 4-6 required terms, 8-10 preferred terms, 12-13 anti-affinity kind,
 // 16-25 app group (spec S11)
+__device__ __forceinline__ uint32_t pod_sid(uint32_t flags) { return (flags >> 2) & 3u; }
 __device__ __forceinline__ uint32_t pod_aa(uint32_t flags) { return (flags >> 12) & 3u; }
 __device__ __forceinline__ uint32_t pod_app(uint32_t flags) { return (flags >> 16) & 1023u; }
 // Required anti-affinity of a batched-mode pod against node i (state at batch start).
@@ -129,10 +134,11 @@ struct DevCfg {
     // the loops whose two-resource scorers skip the zero-allocatable selects (fit_bal_total<F, true>).
     // 0 runs the generic code.
     uint32_t all_alloc;
-    // kFeatStrat only: the shape function of RequestedToCapacityRatio as a device table of 128 bytes,
-    // entry p = raw(p) scaled to 0..100 for the utilisation p in 0..100 (qs_shape_table), written once
-    // before any launch that reads it; nullptr = MostAllocated (raw is the identity, nothing is
-    // looked up).  The pointer's halves sit in strat_tab_lo / strat_tab_hi above, the two words that
+    // kFeatStrat only: the shape functions of RequestedToCapacityRatio as device tables, 128 bytes per
+    // QoS class (the table of class q at byte 128 q; a class with another strategy holds zeros), entry
+    // p = raw(p) scaled to 0..100 for the utilisation p in 0..100 (qs_shape_table), written before any
+    // launch that reads them; nullptr = no class scores RequestedToCapacityRatio (nothing is looked
+    // up).  The pointer's halves sit in strat_tab_lo / strat_tab_hi above, the two words that
     // were padding, so the record's size and every other member's kernel-argument offset stay as
     // they were and the LeastAllocated kernels compile to the code they compiled to before.
     __host__ __device__ const uint8_t *strat_tab() const {
@@ -140,6 +146,14 @@ struct DevCfg {
     }
 };
 static_assert(sizeof(DevCfg) == 112, "DevCfg is a kernel argument of every scoring kernel: keep its layout");
+#define QS_DEVCFG_AT(m, o) static_assert(offsetof(DevCfg, m) == (o), "DevCfg::" #m " moved")
+QS_DEVCFG_AT(wc, 0); QS_DEVCFG_AT(wm, 4); QS_DEVCFG_AT(yd_both, 8); QS_DEVCFG_AT(yd_c, 16); QS_DEVCFG_AT(yd_m, 24);
+QS_DEVCFG_AT(wtt, 32); QS_DEVCFG_AT(wna, 36); QS_DEVCFG_AT(feat, 40); QS_DEVCFG_AT(ba_skip_be, 44);
+QS_DEVCFG_AT(we0, 48); QS_DEVCFG_AT(we1, 52); QS_DEVCFG_AT(bal, 56); QS_DEVCFG_AT(strat_tab_lo, 60);
+QS_DEVCFG_AT(ready, 64); QS_DEVCFG_AT(epoch, 72); QS_DEVCFG_AT(werr, 80); QS_DEVCFG_AT(inject, 88);
+QS_DEVCFG_AT(strat_tab_hi, 92); QS_DEVCFG_AT(first_ticks, 96); QS_DEVCFG_AT(sel_diag, 104);
+QS_DEVCFG_AT(all_alloc, 108);
+#undef QS_DEVCFG_AT
 
 // Resolver prologue: thread 0 spins (s_sleep) until window s0/K's lists are published, then every
 // thread proceeds.  Bounded: after 0.5 s (s_memrealtime, 100 MHz) it records a timeout; once one is
@@ -647,23 +661,42 @@ template <uint32_t F, bool FA = false, class R, class P>
 __device__ __forceinline__ uint32_t la_score(const R &r, const RowX &x, const P &p, const DevCfg &c) {
     const bool hc = r.ac != 0, hm = r.am != 0;
     if constexpr ((F & kFeatStrat) != 0) {
-        // MostAllocated / RequestedToCapacityRatio over the configured list (spec S5 "Scoring
-        // strategies"): per entry the utilisation 0..100 of (alloc, reqd) as LeastAllocated pairs
-        // them; an entry with alloc == 0 (or an extended resource the pod does not request) is not
-        // counted.  The strategy is a kernel argument (wave-uniform: a table means
-        // RequestedToCapacityRatio): one scalar branch picks the form.
+        // The pod's strategy over the configured list (spec S5 "Scoring strategies", S9 "Strategy per
+        // QoS class"): the host writes the strategy of the pod's QoS class into the record (pod_sid)
+        // and keeps one 128-byte shape table per class behind strat_tab().  Per entry the pair
+        // (alloc, reqd) is the one LeastAllocated takes; an entry with alloc == 0 (or an extended
+        // resource the pod does not request) is not counted.  Every caller scores one pod per wave
+        // (the record comes from a uniform index: kernel argument, scalar load, load_vgpr or an LDS
+        // broadcast), so the selector is made scalar and scalar branches pick the form.  The
+        // branches hold no cross-lane operation.  (Sharing the division between the forms, with a
+        // select on each numerator, was measured slower than the three branches: DESIGN.md §3.3.)
         const ExtTerms e = ext_terms(x, p);
+        uint32_t wce = hc ? (uint32_t)c.wc : 0u, wme = hm ? (uint32_t)c.wm : 0u;
+        uint32_t w0 = e.h0 ? (uint32_t)c.we0 : 0u, w1 = e.h1 ? (uint32_t)c.we1 : 0u;
+        const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)pod_sid(p.flags));
+        if (sid == 0u) {
+            // LeastAllocated: the kFeatRes form below, term for term
+            const uint32_t sc_c = least_requested(r.ac, r.zc + p.zc, r.yc);
+            uint32_t sc_m;
+            if constexpr (std::is_same<R, RowW>::value) sc_m = least_requested_w(r.am, r.zm + p.zm, r.ym);
+            else sc_m = least_requested(r.am, r.zm + p.zm, r.ym);
+            const uint32_t s0 = least_requested(x.ae0, x.re0 + p.re0, e.y0);
+            const uint32_t s1 = least_requested(x.ae1, x.re1 + p.re1, e.y1);
+            return div_small(__umul24(sc_c, wce) + __umul24(sc_m, wme) + __umul24(s0, w0) + __umul24(s1, w1),
+                             wce + wme + w0 + w1);
+        }
         uint32_t uc = utilization(r.ac, r.zc + p.zc, r.yc), um;
         if constexpr (std::is_same<R, RowW>::value) um = utilization_w(r.am, r.zm + p.zm, r.ym);
         else um = utilization(r.am, r.zm + p.zm, r.ym);
         uint32_t u0 = utilization(x.ae0, x.re0 + p.re0, e.y0), u1 = utilization(x.ae1, x.re1 + p.re1, e.y1);
-        uint32_t wce = hc ? (uint32_t)c.wc : 0u, wme = hm ? (uint32_t)c.wm : 0u;
-        uint32_t w0 = e.h0 ? (uint32_t)c.we0 : 0u, w1 = e.h1 ? (uint32_t)c.we1 : 0u;
         const uint8_t *tb = c.strat_tab();
-        if (tb != nullptr) {
-            // raw(p) from the 101-entry table (indices are 0..100 by construction; the min keeps a
-            // read inside the 128-byte buffer whatever the row holds); four independent byte loads,
-            // issued together.  A resource whose score is 0 does not count towards the weight sum.
+        if (sid == 2u && tb != nullptr) {
+            // raw(p) from the class's 101-entry table (indices are 0..100 by construction; the min keeps
+            // a read inside the 128-byte table whatever the row holds, and the class id is 0..2 of a
+            // 3 x 128-byte buffer); four independent byte loads, issued together.  A resource whose
+            // score is 0 does not count towards the weight sum.
+            const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.flags & 3u));
+            tb += 128u * (q < 2u ? q : 2u);
             uc = tb[uc < 100u ? uc : 100u]; um = tb[um < 100u ? um : 100u];
             u0 = tb[u0 < 100u ? u0 : 100u]; u1 = tb[u1 < 100u ? u1 : 100u];
             wce = uc ? wce : 0u; wme = um ? wme : 0u; w0 = u0 ? w0 : 0u; w1 = u1 ? w1 : 0u;

@@ -127,10 +127,17 @@ uint32_t res_feat(const qs_config &c, bool has_ext) {
     generic |= set != ((1u << QS_RES_CPU) | (1u << QS_RES_MEMORY));
     return generic ? (kFeatRes | kFeatExt) : 0u;
 }
-// MostAllocated / RequestedToCapacityRatio run the kFeatStrat kernels whatever the lists are: such a
-// stream (or pod) never reduces to the default two-resource kernels, which compute LeastAllocated.
-uint32_t strat_feat(const qs_ctx *c) {
-    return c->strat != QS_STRATEGY_LEAST_ALLOCATED ? (kFeatStrat | kFeatRes | kFeatExt) : 0u;
+// A stream (or pod) runs the kFeatStrat kernels, whatever the lists are, when some pod of it belongs
+// to a QoS class whose strategy is not LeastAllocated; otherwise every pod of it scores
+// LeastAllocated and it reduces as res_feat says (the same kind of exact reduction: the kFeatStrat
+// kernels compute the kFeatRes score for such a pod).
+uint32_t strat_feat(const qs_ctx *c, const qs_pod *pods, uint32_t p) {
+    if (c->strat[0].type == QS_STRATEGY_LEAST_ALLOCATED && c->strat[1].type == QS_STRATEGY_LEAST_ALLOCATED &&
+        c->strat[2].type == QS_STRATEGY_LEAST_ALLOCATED)
+        return 0u;
+    for (uint32_t j = 0; j < p; j++)
+        if (c->strat[pods[j].qos].type != QS_STRATEGY_LEAST_ALLOCATED) return kFeatStrat | kFeatRes | kFeatExt;
+    return 0u;
 }
 
 DevCfg make_devcfg(const qs_config &c) {
@@ -426,11 +433,12 @@ void check_pod(const qs_pod &p, uint32_t j) {
 
 // NodeAffinity disabled (config.enable_affinity = 0): the pod's required / preferred term counts are
 // recorded as 0, so the normalizing kernels (which evaluate both plugins) neither filter nor score
-// by affinity.
+// by affinity.  Bits 2-3: the strategy of the pod's QoS class (qs_scoring_strategy_type), which only
+// the kFeatStrat scorer reads (check_pod has bounded qos to 0..2).
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
-    return (uint32_t)p.qos | (aff * (uint32_t)p.n_req_terms << 4) | (aff * (uint32_t)p.n_pref_terms << 8) |
-           ((uint32_t)p.anti_affinity << 12) | ((uint32_t)p.app << 16);
+    return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
+           (aff * (uint32_t)p.n_pref_terms << 8) | ((uint32_t)p.anti_affinity << 12) | ((uint32_t)p.app << 16);
 }
 
 // Device pod record in the context's layout: DPod (compact, memory in 2^shift units) or DPodW
@@ -739,8 +747,10 @@ void percentile_stats(const std::vector<uint64_t> &st, qs_stats *s) {
 uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, int32_t *on, uint64_t *ok,
                      KernelTimer &kt) {
     const uint32_t n = c->m.n, P = s->p;
-    if (c->dc.feat & kFeatStrat)
-        fail(QS_EINVAL, "QS_MODE_BATCHED scores LeastAllocated only (qs_set_scoring_strategy)");
+    for (int q = 0; q < 3; q++)
+        if (c->strat[q].type != QS_STRATEGY_LEAST_ALLOCATED)
+            fail(QS_EINVAL, "QS_MODE_BATCHED scores LeastAllocated only (qs_set_scoring_strategy[_qos]: class " +
+                                std::to_string(q) + " has another strategy)");
     if (c->dc.feat & (kFeatTaint | kFeatAffinity))
         fail(QS_EINVAL, "QS_MODE_BATCHED supports the Fit + Balanced (+ extended resources) profile");
     if (!c->dt.apps) fail(QS_EINVAL, "QS_MODE_BATCHED keeps anti-affinity state for tables up to 2^20 nodes");
@@ -942,31 +952,77 @@ qs_status qs_shape_table(const qs_shape_point *shape, uint32_t n, uint8_t table[
     return QS_OK;
 }
 
+// Validates one strategy and writes its device table (RequestedToCapacityRatio: the shape function;
+// the other types take none and hold zeros).  Throws QS_EINVAL with the reason.
+static void strategy_table(const qs_scoring_strategy *s, uint8_t tab[128]) {
+    if (!s) fail(QS_EINVAL, "null scoring strategy");
+    if (s->type != QS_STRATEGY_LEAST_ALLOCATED && s->type != QS_STRATEGY_MOST_ALLOCATED &&
+        s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO)
+        fail(QS_EINVAL, "unknown scoring strategy type");
+    if (s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO && s->n_shape != 0)
+        fail(QS_EINVAL, "a shape is given for a scoring strategy that takes none");
+    std::memset(tab, 0, 128);
+    if (s->type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO) {
+        if (s->n_shape < 1 || s->n_shape > QS_MAX_SHAPE) fail(QS_EINVAL, "shape: 1 to 16 points");
+        shape_table(s->shape, (uint32_t)s->n_shape, tab);
+    }
+}
+
+// Stores the strategy of the classes q0..q1 (validated, tab its table) and uploads all three tables.
+static void set_strategy(qs_ctx *c, int q0, int q1, const qs_scoring_strategy *s, const uint8_t tab[128]) {
+    if (!c->streams.empty()) fail(QS_ESTATE, "the scoring strategy cannot change while prepared streams exist");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));  // no launch of this context still reads the tables
+    alignas(16) uint8_t all[3 * 128];
+    qs_scoring_strategy next[3] = {c->strat[0], c->strat[1], c->strat[2]};
+    for (int q = 0; q < 3; q++) {
+        if (q >= q0 && q <= q1) {
+            next[q] = qs_scoring_strategy{};
+            next[q].type = s->type;
+            next[q].n_shape = s->n_shape;
+            for (int i = 0; i < s->n_shape; i++) next[q].shape[i] = s->shape[i];
+            std::memcpy(all + 128 * q, tab, 128);
+        } else {
+            uint8_t t[128];
+            strategy_table(&c->strat[q], t);  // (valid: it was stored through here)
+            std::memcpy(all + 128 * q, t, 128);
+        }
+    }
+    c->strat_tab.ensure(sizeof all);
+    HIPCHK(hipMemcpy(c->strat_tab.p, all, sizeof all, hipMemcpyHostToDevice));
+    bool rtcr = false;
+    for (int q = 0; q < 3; q++) {
+        c->strat[q] = next[q];
+        rtcr |= next[q].type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO;
+    }
+    // DevCfg: the tables when some class scores RequestedToCapacityRatio, else none (kFeatStrat kernels only)
+    const uint64_t tp = rtcr ? (uint64_t)(uintptr_t)c->strat_tab.p : 0;
+    c->dc.strat_tab_lo = (uint32_t)tp;
+    c->dc.strat_tab_hi = (uint32_t)(tp >> 32);
+}
+
 qs_status qs_set_scoring_strategy(qs_ctx *c, const qs_scoring_strategy *s) {
     return guarded(c, [&] {
-        if (!s) fail(QS_EINVAL, "null scoring strategy");
-        if (s->type != QS_STRATEGY_LEAST_ALLOCATED && s->type != QS_STRATEGY_MOST_ALLOCATED &&
-            s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO)
-            fail(QS_EINVAL, "unknown scoring strategy type");
-        if (s->type != QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO && s->n_shape != 0)
-            fail(QS_EINVAL, "a shape is given for a scoring strategy that takes none");
-        alignas(16) uint8_t tab[128] = {0};
-        if (s->type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO) {
-            if (s->n_shape < 1 || s->n_shape > QS_MAX_SHAPE) fail(QS_EINVAL, "shape: 1 to 16 points");
-            shape_table(s->shape, (uint32_t)s->n_shape, tab);
-        } else {
-            for (int p = 0; p <= 100; p++) tab[p] = (uint8_t)p;
-        }
-        if (!c->streams.empty()) fail(QS_ESTATE, "the scoring strategy cannot change while prepared streams exist");
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamSynchronize(c->stream));  // no launch of this context still reads the table
-        c->strat_tab.ensure(sizeof tab);
-        HIPCHK(hipMemcpy(c->strat_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
-        c->strat = s->type;
-        // DevCfg: a table means RequestedToCapacityRatio, none MostAllocated (kFeatStrat kernels only)
-        const uint64_t tp = s->type == QS_STRATEGY_REQUESTED_TO_CAPACITY_RATIO ? (uint64_t)(uintptr_t)c->strat_tab.p : 0;
-        c->dc.strat_tab_lo = (uint32_t)tp;
-        c->dc.strat_tab_hi = (uint32_t)(tp >> 32);
+        uint8_t tab[128];
+        strategy_table(s, tab);
+        set_strategy(c, 0, 2, s, tab);
+    });
+}
+
+qs_status qs_set_scoring_strategy_qos(qs_ctx *c, int32_t qos, const qs_scoring_strategy *s) {
+    return guarded(c, [&] {
+        if (qos < 0 || qos > 2) fail(QS_EINVAL, "qos must be 0 (BestEffort), 1 (Burstable) or 2 (Guaranteed)");
+        uint8_t tab[128];
+        strategy_table(s, tab);
+        set_strategy(c, qos, qos, s, tab);
+    });
+}
+
+qs_status qs_get_scoring_strategy_qos(qs_ctx *c, int32_t qos, qs_scoring_strategy *out) {
+    return guarded(c, [&] {
+        if (qos < 0 || qos > 2) fail(QS_EINVAL, "qos must be 0 (BestEffort), 1 (Burstable) or 2 (Guaranteed)");
+        if (!out) fail(QS_EINVAL, "null scoring strategy");
+        *out = c->strat[qos];
     });
 }
 
@@ -1311,7 +1367,7 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
     DevCfg dc = c->dc;
     const bool pod_ext = pod->req_ext[0] || pod->req_ext[1];
     dc.feat = feat_of(c->cfg) | (pod_ext ? kFeatExt : 0u) | (c->wide ? kFeatWide | kFeatExt : 0u) |
-              res_feat(c->cfg, pod_ext) | strat_feat(c);
+              res_feat(c->cfg, pod_ext) | strat_feat(c, pod, 1);
     wts[2] = (dc.feat & kFeatTaint) ? (uint32_t)dc.wtt : 0u;
     wts[3] = (dc.feat & kFeatAffinity) ? (uint32_t)dc.wna : 0u;
     if (n == 0 || !c->dev_valid) {
@@ -1399,7 +1455,7 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         bool has_ext = false;
         for (uint32_t j = 0; j < p && !has_ext; j++) has_ext = pods[j].req_ext[0] || pods[j].req_ext[1];
         if (has_ext) s->feat |= kFeatExt;
-        s->feat |= res_feat(c->cfg, has_ext) | strat_feat(c);
+        s->feat |= res_feat(c->cfg, has_ext) | strat_feat(c, pods, p);
         s->order = qos_order(pods, p, c->cfg.qos_sort != 0);
         const size_t rb = pod_record_bytes(c->wide);
         std::vector<uint8_t> dp(rb * std::max<uint32_t>(p, 1));

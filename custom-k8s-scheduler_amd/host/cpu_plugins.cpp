@@ -379,19 +379,36 @@ Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy &st) {
     return r;
 }
 
-std::vector<Profile> CPUProfiles(const qs_config &cfg) {
+// One NodeResourcesFit per QoS class.  Upstream's factory receives the profile's PluginConfig args;
+// PluginFactory here takes none, so the class's instance is registered under a key of its own
+// (CPUFitKey) that the class's profile names.  Name() stays NodeResourcesFit.
+std::string CPUFitKey(int qos) { return std::string(kNodeResourcesFit) + "/" + kProfileName[std::clamp(qos, 0, 2)]; }
+
+Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy (&st)[3]) {
+    Registry r = CPURegistry(cfg);
+    for (int q = 0; q < 3; ++q) {
+        const qs_scoring_strategy sq = st[q];
+        r[CPUFitKey(q)] = [cfg, sq](Handle *h) { return std::make_shared<NodeResourcesFit>(cfg, sq, h); };
+    }
+    return r;
+}
+
+std::vector<Profile> CPUProfiles(const qs_config &cfg) { return CPUProfiles(cfg, false); }
+
+std::vector<Profile> CPUProfiles(const qs_config &cfg, bool per_class_fit) {
     std::vector<Profile> out;
     for (int q = 0; q < 3; ++q) {
+        const std::string fit = per_class_fit ? CPUFitKey(q) : std::string(kNodeResourcesFit);
         Profile p;
         p.scheduler_name = kProfileName[q];
         p.queue_sort = kCPUQoSSort;
-        p.pre_filter = {{kNodeResourcesFit}};
+        p.pre_filter = {{fit}};
         // upstream's default filter order: TaintToleration, NodeAffinity, ..., NodeResourcesFit
         if (cfg.enable_taint) p.filter.push_back({kTaintToleration});
         if (cfg.enable_affinity) p.filter.push_back({kNodeAffinity});
-        p.filter.push_back({kNodeResourcesFit});
-        auto add = [&](const char *n, int32_t w) { if (w > 0) p.score.push_back({n, w}); };
-        add(kNodeResourcesFit, cfg.w_fit[q]);
+        p.filter.push_back({fit});
+        auto add = [&](const std::string &n, int32_t w) { if (w > 0) p.score.push_back({n, w}); };
+        add(fit, cfg.w_fit[q]);
         add(kNodeResourcesBalancedAllocation, cfg.w_bal[q]);
         if (cfg.enable_taint) add(kTaintToleration, cfg.w_taint);
         if (cfg.enable_affinity) add(kNodeAffinity, cfg.w_affinity);

@@ -42,6 +42,12 @@ Registry CPURegistry(const qs_config &cfg);
 // ... with NodeResourcesFitArgs.ScoringStrategy.Type (and the RequestedToCapacityRatio shape, assumed
 // valid: qs_shape_table checks one); the one-argument form scores LeastAllocated
 Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy &strategy);
+// ... with one strategy per QoS class (strategy[q]: 0 BestEffort, 1 Burstable, 2 Guaranteed; spec S9
+// "Strategy per QoS class"), as upstream's one KubeSchedulerProfile per class with its own
+// NodeResourcesFitArgs: class q's NodeResourcesFit instance is registered as CPUFitKey(q), and
+// CPUProfiles(cfg, true) makes the class's profile use it
+Registry CPURegistry(const qs_config &cfg, const qs_scoring_strategy (&strategy)[3]);
+std::string CPUFitKey(int qos);
 // The scorer itself over n (allocatable, requested, weight) entries (spec S5 "Scoring strategies")
 int64_t FitStrategyScore(const qs_scoring_strategy &strategy, const int64_t *alloc, const int64_t *reqd,
                          const int64_t *weight, int n);
@@ -49,6 +55,8 @@ int64_t FitStrategyScore(const qs_scoring_strategy &strategy, const int64_t *all
 // w_fit[q], NodeResourcesBalancedAllocation w_bal[q], TaintToleration w_taint / NodeAffinity
 // w_affinity when enabled.
 std::vector<Profile> CPUProfiles(const qs_config &cfg);
+// per_class_fit: profile q's NodeResourcesFit is the instance CPUFitKey(q) of the three-strategy registry
+std::vector<Profile> CPUProfiles(const qs_config &cfg, bool per_class_fit);
 std::string CPUProfileOf(const Pod &, const PodResources &r);
 
 }  // namespace qsfw

@@ -24,6 +24,17 @@ GpuBackend::GpuBackend(const qs_config &cfg, const qs_scoring_strategy &strategy
     }
 }
 
+GpuBackend::GpuBackend(const qs_config &cfg, const qs_scoring_strategy (&strategy)[3], int device)
+    : GpuBackend(cfg, device) {
+    for (int q = 0; q < 3; ++q) {
+        if (qs_set_scoring_strategy_qos(ctx_, q, &strategy[q]) == QS_OK) continue;
+        const std::string why = err("qs_set_scoring_strategy_qos");
+        qs_close(ctx_);  // (the destructor does not run when a constructor throws)
+        ctx_ = nullptr;
+        throw std::runtime_error(why);
+    }
+}
+
 GpuBackend::~GpuBackend() {
     if (ctx_) qs_close(ctx_);
 }

@@ -48,6 +48,9 @@ class GpuBackend {
     // ... with NodeResourcesFitArgs.ScoringStrategy.Type / the RequestedToCapacityRatio shape passed to
     // the context (qs_set_scoring_strategy); a rejected strategy throws std::runtime_error with the reason.
     GpuBackend(const qs_config &cfg, const qs_scoring_strategy &strategy, int device = 0);
+    // ... with one strategy per QoS class (strategy[q]; qs_set_scoring_strategy_qos): the QoSGPU plugin of
+    // every profile shares the one context, which scores each pod with its class's strategy
+    GpuBackend(const qs_config &cfg, const qs_scoring_strategy (&strategy)[3], int device = 0);
     ~GpuBackend();
     GpuBackend(const GpuBackend &) = delete;
     GpuBackend &operator=(const GpuBackend &) = delete;

@@ -19,7 +19,7 @@ import numpy as np
 
 from ._abi import (ENGINES, ENGINE_NAMES, EXPORTED, LIB_PATH, POD_DTYPE, QS_ABI_VERSION,
                    QS_MAX_EXT, QS_MAX_SCORE_RES, QS_MAX_TERMS, QS_MODE_BATCHED, QS_MODE_EXACT, QS_OK,
-                   RESOURCES, FIT_REASONS, QS_FIT_TAINT, QS_MAX_SHAPE, STRATEGIES, QschedError,
+                   RESOURCES, FIT_REASONS, QS_FIT_TAINT, QS_MAX_SHAPE, QOS_NAMES, STRATEGIES, QschedError,
                    QschedLibraryMissing, QsConfig, QsContainer, QsNodeRow, QsNodeSoa, QsScoringStrategy,
                    QsStats, load)
 
@@ -133,6 +133,9 @@ class Scheduler:
         # NodeResourcesFitArgs.ScoringStrategy.Type / RequestedToCapacityRatio.Shape are not part of
         # qs_config: they are set on the open context (qs_set_scoring_strategy)
         strategy, shape = config.pop("scoring_strategy", None), config.pop("shape", None)
+        # ... and per QoS class (one upstream profile each): {"BestEffort": dict(scoring_strategy=...,
+        # shape=...), ...}, applied after a context-wide scoring_strategy
+        qos_strategies = config.pop("qos_strategies", None)
         self.cfg = Config(config).to_c()
         ctx = ctypes.c_void_p()
         if shard is None:
@@ -147,16 +150,24 @@ class Scheduler:
             raise QschedError(st, "qs_open failed: " + (why.decode() if why else "no HIP device?"))
         self.ctx = ctx
         self.n = 0
-        if strategy is not None or shape is not None:
-            try:
+        try:
+            if strategy is not None or shape is not None:
                 self.set_scoring_strategy(strategy or "LeastAllocated", shape)
-            except Exception:
-                self.close()
-                raise
+            for q, sc in (qos_strategies or {}).items():
+                self.set_scoring_strategy(sc.get("scoring_strategy") or "LeastAllocated", sc.get("shape"), qos=q)
+        except Exception:
+            self.close()
+            raise
 
-    def set_scoring_strategy(self, strategy, shape=None):
+    @staticmethod
+    def _qos_id(qos) -> int:
+        return QOS_NAMES[qos] if isinstance(qos, str) else int(qos)
+
+    def set_scoring_strategy(self, strategy, shape=None, qos=None):
         """qs_set_scoring_strategy: "LeastAllocated" | "MostAllocated" | "RequestedToCapacityRatio"
-        (or the qs_scoring_strategy_type id) and, for the last, shape = [(utilization, score), ...]."""
+        (or the qs_scoring_strategy_type id) and, for the last, shape = [(utilization, score), ...].
+        qos = "BestEffort" | "Burstable" | "Guaranteed" (or 0..2) sets the strategy of that QoS class
+        only (qs_set_scoring_strategy_qos); None sets all three."""
         shape = list(shape or [])
         if len(shape) > QS_MAX_SHAPE:
             raise ValueError(f"at most {QS_MAX_SHAPE} shape points")
@@ -165,7 +176,17 @@ class Scheduler:
         st.n_shape = len(shape)
         for i, (u, sc) in enumerate(shape):
             st.shape[i][0], st.shape[i][1] = int(u), int(sc)
-        self._chk(self.lib.qs_set_scoring_strategy(self.ctx, ctypes.byref(st)))
+        if qos is None:
+            self._chk(self.lib.qs_set_scoring_strategy(self.ctx, ctypes.byref(st)))
+        else:
+            self._chk(self.lib.qs_set_scoring_strategy_qos(self.ctx, self._qos_id(qos), ctypes.byref(st)))
+
+    def get_scoring_strategy(self, qos):
+        """qs_get_scoring_strategy_qos: (strategy name, [(utilization, score), ...]) of one QoS class."""
+        st = QsScoringStrategy()
+        self._chk(self.lib.qs_get_scoring_strategy_qos(self.ctx, self._qos_id(qos), ctypes.byref(st)))
+        name = {v: k for k, v in STRATEGIES.items()}[int(st.type)]
+        return name, [(int(st.shape[i][0]), int(st.shape[i][1])) for i in range(int(st.n_shape))]
 
     def mailbox_export(self) -> bytes:
         """qs_dist_mailbox_export: this rank's 64-byte mailbox IPC handle (sharded contexts opened

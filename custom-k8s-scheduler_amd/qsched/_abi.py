@@ -33,6 +33,8 @@ RESOURCES = {"cpu": 1, "memory": 2, "ext0": 3, "ext1": 4}
 
 # qs_scoring_strategy_type (NodeResourcesFitArgs.ScoringStrategy.Type)
 STRATEGIES = {"LeastAllocated": 0, "MostAllocated": 1, "RequestedToCapacityRatio": 2}
+# QoS class ids (qs_pod.qos; spec S9)
+QOS_NAMES = {"BestEffort": 0, "Burstable": 1, "Guaranteed": 2}
 QS_MAX_SHAPE = 16
 
 QS_OK, QS_EINVAL, QS_EDEVICE, QS_ETIMEOUT, QS_ENOMEM, QS_ESTATE = range(6)
@@ -147,6 +149,8 @@ _SIGS = {
     "qs_dist_mailbox_export": (ctypes.c_int, [_P, _P]),
     "qs_dist_mailbox_connect": (ctypes.c_int, [_P, _P]),
     "qs_set_scoring_strategy": (ctypes.c_int, [_P, _P]),
+    "qs_set_scoring_strategy_qos": (ctypes.c_int, [_P, ctypes.c_int32, _P]),
+    "qs_get_scoring_strategy_qos": (ctypes.c_int, [_P, ctypes.c_int32, _P]),
     "qs_shape_table": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "qs_close": (ctypes.c_int, [_P]),
     "qs_last_error": (ctypes.c_char_p, [_P]),

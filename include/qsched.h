@@ -12,6 +12,10 @@
  *   qs_set_scoring_strategy   NodeResourcesFitArgs.ScoringStrategy.Type / RequestedToCapacityRatio.Shape
  *                             (UP apis/config/types_pluginargs.go#ScoringStrategy; noderesources/fit.go#NewFit
  *                             picks the scorer from nodeResourceStrategyTypeMap)
+ *   qs_set_scoring_strategy_qos  the same of one QoS class: upstream gives every KubeSchedulerProfile its own
+ *                             NodeResourcesFitArgs.ScoringStrategy (UP apis/config/types.go#KubeSchedulerProfile.
+ *                             PluginConfig; profile.NewMap builds one framework, and so one Fit instance, per
+ *                             profile), and a QoS class is one profile here (spec S9)
  *   qs_nodes_load             Cache.UpdateSnapshot → Snapshot NodeInfo list (UP backend/cache#Snapshot)
  *   qs_node_upsert            per-NodeInfo Generation diff (UP framework/types.go#NodeInfo.Generation)
  *   qs_score_pod              PreFilter+Filter+PreScore+Score+NormalizeScore for ALL nodes of one pod
@@ -266,6 +270,14 @@ QS_API qs_status qs_dist_mailbox_connect(qs_ctx *ctx, const uint8_t *handles /* 
  * strictly increasing, score outside 0..10), or a shape given for a type that takes none.
  * QS_MODE_BATCHED runs LeastAllocated only: with another strategy set qs_stream_run returns QS_EINVAL. */
 QS_API qs_status qs_set_scoring_strategy(qs_ctx *ctx, const qs_scoring_strategy *s);
+/* The scoring strategy of one QoS class (qos 0 BestEffort, 1 Burstable, 2 Guaranteed; spec S9 "Strategy
+ * per QoS class"): the fit score of a pod on every node is computed with the strategy of the pod's class,
+ * type and shape both.  qs_set_scoring_strategy above sets all three classes.  The same validation and
+ * QS_ESTATE rule; QS_EINVAL for qos outside 0..2.  A stream whose pods all belong to LeastAllocated
+ * classes runs the kernels a default context runs.  QS_MODE_BATCHED returns QS_EINVAL while any class
+ * has another strategy.  qs_get_scoring_strategy_qos returns what is stored for the class. */
+QS_API qs_status qs_set_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, const qs_scoring_strategy *s);
+QS_API qs_status qs_get_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, qs_scoring_strategy *out);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);

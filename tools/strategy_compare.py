@@ -9,7 +9,11 @@ Arms per configuration:
                   list {cpu:1, memory:1, amd.com/gpu:5} / Balanced [cpu, memory, amd.com/gpu], which does
                   not reduce; config 2, whose pods request no extended resource, with QS_FORCE_RES=1
   most, rtcr_binpack, rtcr_three   the same lists as least_res under the new strategies
+  mix             one strategy per QoS class: BestEffort MostAllocated, Burstable
+                  RequestedToCapacityRatio (the three-segment shape), Guaranteed LeastAllocated, on the
+                  same lists; checked against tests/qos_strategy_ref.py
 least_res is the yardstick of the new scorers: the same kernel family with the same Balanced path.
+--arms picks a subset (a comparison against another tree runs the arms both trees know).
 
 Each arm runs in a process of its own (QS_FORCE_RES is read once), is checked bit for bit against
 tests/strategy_ref.py on the first 2,000 pods scheduled as a stream of their own, and prints pods/s
@@ -36,6 +40,9 @@ STRATS = {
     "most": dict(scoring_strategy="MostAllocated"),
     "rtcr_binpack": dict(scoring_strategy="RequestedToCapacityRatio", shape=[(0, 0), (100, 10)]),
     "rtcr_three": dict(scoring_strategy="RequestedToCapacityRatio", shape=THREE),
+    "mix": dict(qos_strategies={"BestEffort": dict(scoring_strategy="MostAllocated"),
+                                "Burstable": dict(scoring_strategy="RequestedToCapacityRatio", shape=THREE),
+                                "Guaranteed": dict(scoring_strategy="LeastAllocated")}),
 }
 SIZES = {2: (5000, 100000), 4: (5000, 150000)}
 
@@ -51,7 +58,7 @@ def arm_cfg(config, arm):
 def run_arm(config, arm, steps, prefix):
     import numpy as np
 
-    import strategy_ref as R
+    import qos_strategy_ref as R  # (strategy_ref's loop; the same placements where no class is listed)
     from qsched import Scheduler, synth_generate
 
     n, p = SIZES[config]
@@ -87,6 +94,7 @@ def run_arm(config, arm, steps, prefix):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--configs", default="2,4")
+    ap.add_argument("--arms", default=",".join(STRATS))
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--prefix", type=int, default=2000)
     ap.add_argument("--one", nargs=2, metavar=("CONFIG", "ARM"), help="run one arm in this process")
@@ -96,7 +104,7 @@ def main():
         return 0
     rows, bad = [], 0
     for config in (int(c) for c in a.configs.split(",")):
-        for arm in STRATS:
+        for arm in a.arms.split(","):
             env = dict(os.environ)
             env.pop("QS_FORCE_RES", None)
             if config == 2 and arm != "least_default":
