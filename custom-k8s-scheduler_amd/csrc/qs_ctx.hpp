@@ -104,6 +104,14 @@ struct qs_stream {
     uint64_t epoch_after = 0;  // the context's table epoch right after the last run (FitError replay)
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
+    // Uniform windows: run0[k] = first stream position of the run of byte-identical
+    // device pod records that holds position k (qs_stream_prepare); the bitmap of the windows of
+    // uni_K pods that lie inside one run, on the device, rebuilt when a run plans another K;
+    // uni_given = uniform windows the last resident launch was given (qs_stream_uniform_windows)
+    std::vector<uint32_t> run0;
+    std::vector<uint32_t> uni_bits;
+    qs_host::DevBuf d_uni;
+    uint32_t uni_K = 0, uni_count = 0, uni_given = 0;
     qs_ctx *owner = nullptr;  // the context that lists this stream (qs_ctx::streams); nullptr once it closed
     // LOOKAHEAD window sequence as an instantiated HIP graph, valid while gkey matches
     hipGraphExec_t gexec = nullptr;

@@ -452,6 +452,14 @@ __device__ __forceinline__ void reserve(R &r, RowX &x, const P &p, int sign) {
     r.np += sign;
     x.re0 += sign * p.re0; x.re1 += sign * p.re1;
 }
+// k Reserves of the same pod at once (the resident resolver's windows of identical pods)
+template <class R, class P>
+__device__ __forceinline__ void reserve_n(R &r, RowX &x, const P &p, int k) {
+    r.rc += k * p.rc; r.rm += k * p.rm;
+    r.zc += k * p.zc; r.zm += k * p.zm;
+    r.np += k;
+    x.re0 += k * p.re0; x.re1 += k * p.re1;
+}
 
 // ---- spec S4: NodeResourcesFit.Filter (UP noderesources/fit.go#fitsRequest) ------------------
 // Per-resource checks are skipped for zero requests, which also covers the all-zero early return.

@@ -538,7 +538,10 @@ void ensure_layout(qs_ctx *c, const qs_pod *pods, uint32_t p, int extra_shift = 
     want = std::max(0, want);
     bool wide = c->wide;
     for (uint32_t i = 0; i < m.n; i++) {
-        // pods this node can still take (+1: the evaluation of one more before Fit rejects it)
+        // pods this node can still take (+1: the evaluation of one more before Fit rejects it).
+        // The resident resolver's uniform-window ladders (la_resolve4_stream) score up to kResUniR
+        // pods past that point; those rungs may wrap, and are never read: the first infeasible rung
+        // of a ladder is 0 and no rung behind it is ever reached.
         const __int128 more = (__int128)std::max<int64_t>(0, m.mp[i] - m.np[i]) + 1;
         if ((__int128)m.zc[i] + more * nzc > kGrowLimit32)
             fail(QS_EINVAL, "node " + std::to_string(i) + ": NonZeroRequested cpu could pass 2^31 m during the stream");
@@ -1466,6 +1469,11 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
             compact_pod(c, pods[j], j, c->shift, c->wide, dp.data() + rb * k);
             if (needx) dx[k] = compact_podx(c, pods[j]);
         }
+        // runs of byte-identical device records (a Deployment's replicas, the BestEffort tail of a
+        // QoS-sorted stream): the resident resolver's uniform windows
+        s->run0.resize(p);
+        for (uint32_t k = 0; k < p; k++)
+            s->run0[k] = k > 0 && std::memcmp(dp.data() + rb * k, dp.data() + rb * (k - 1), rb) == 0 ? s->run0[k - 1] : k;
         const size_t P1 = std::max<uint32_t>(p, 1);
         s->d_pods.ensure(rb * P1);
         s->d_podx.ensure(sizeof(DPodX) * dx.size());
@@ -1497,6 +1505,7 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         // replay now; only a successful run sets them again below
         s->ran = false;
         s->mode_ran = -1;
+        s->uni_given = 0;
         ++c->table_epoch;
         if (!c->dev_valid) upload_table(c);  // recovery after a device fault: rebuild from the mirror
         const uint32_t n = c->m.n, P = s->p;
@@ -1875,12 +1884,40 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                         rdiag = c->diag.as<uint64_t>();
                         HIPCHK(hipMemsetAsync(rdiag, 0, 1024, c->stream));
                     }
+                    // windows of identical pod records, for the K this launch runs (QS_RES_UNIFORM=0:
+                    // none, read per run: tests and A/B timing run both paths from one library)
+                    const char *ue = getenv("QS_RES_UNIFORM");
+                    const uint32_t *uni = nullptr;
+                    s->uni_given = 0;
+                    if (!(ue && ue[0] == '0') && la_stream_res_takes_uniform(rgeo, c->dc.feat, rsh.W) &&
+                        s->run0.size() == P) {
+                        if (s->uni_K != rgeo.K) {
+                            const uint32_t K = rgeo.K, nwin = (P + K - 1) / K;
+                            s->uni_bits.assign((nwin + 31) / 32 + 1, 0u);
+                            s->uni_count = 0;
+                            for (uint32_t w = 0; w < nwin; ++w) {
+                                const uint32_t s0 = w * K, last = std::min(P, s0 + K) - 1;
+                                if (s->run0[last] <= s0) {
+                                    s->uni_bits[w >> 5] |= 1u << (w & 31);
+                                    ++s->uni_count;
+                                }
+                            }
+                            s->d_uni.ensure(4 * s->uni_bits.size());
+                            HIPCHK(hipMemcpyAsync(s->d_uni.p, s->uni_bits.data(), 4 * s->uni_bits.size(),
+                                                  hipMemcpyHostToDevice, c->stream));
+                            s->uni_K = K;
+                        }
+                        if (s->uni_count) {
+                            uni = s->d_uni.as<uint32_t>();
+                            s->uni_given = s->uni_count;
+                        }
+                    }
                     kt.begin(3, c->stream);  // the one launch, under "resolve"
                     HIPCHK(launch_la_stream_res(c->dt, dp, dx, dcr, P, rgeo, L0, c->clists.as<uint64_t>(),
                                                 (uint32_t)lwords, (uint32_t)rcw, c->npart.as<uint4>(),
                                                 c->normi.as<NormInfo>(), c->nstat.as<uint32_t>(),
                                                 c->nfall.as<unsigned long long>(), on, ok,
-                                                st, c->resctl.p, sel, rdiag, rsh, c->stream));
+                                                st, c->resctl.p, sel, rdiag, rsh, c->stream, uni));
                     kt.end(3, c->stream);
                     if (rdiag) {
                         uint64_t h[128] = {0};
@@ -1907,6 +1944,11 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                         if (h[36] + h[37] + h[38])
                             fprintf(stderr, "QS_RES_DIAG B3 -> B1 busy (ns per window, without the B1 wait): D %.0f, A %.0f, "
                                             "C %.0f\n", h[38] * 10.0 / nw, h[37] * 10.0 / nw, h[36] * 10.0 / nw);
+                        if (h[41])
+                            fprintf(stderr, "QS_RES_DIAG uniform windows %llu: %.2f us each from B1 to the window end, "
+                                            "%.2f rounds each; the other windows %.2f us each, boundaries included\n",
+                                    (unsigned long long)h[41], h[40] * 0.01 / (double)h[41], (double)h[42] / (double)h[41],
+                                    h[3] > h[41] ? (h[1] - h[40]) * 0.01 / (double)(h[3] - h[41]) : 0.0);
                         if (h[33])
                             fprintf(stderr, "QS_RES_DIAG last list of a window published %.2f us after the start of "
                                             "the window before it (%llu windows; after 13 us %llu, after 15 us %llu)\n",
@@ -2259,6 +2301,13 @@ qs_status qs_stream_stamps(qs_ctx *c, qs_stream *s, uint64_t *stamps) {
     return guarded(c, [&] {
         if (!s || !s->ran || !s->d_stamp.p) fail(QS_ESTATE, "no timestamps recorded");
         HIPCHK(hipMemcpy(stamps, s->d_stamp.p, 8 * (size_t)s->p, hipMemcpyDeviceToHost));
+    });
+}
+
+qs_status qs_stream_uniform_windows(qs_ctx *c, qs_stream *s, uint32_t *windows) {
+    return guarded(c, [&] {
+        if (!s || !windows) fail(QS_EINVAL, "null stream or output");
+        *windows = s->ran ? s->uni_given : 0u;
     });
 }
 

@@ -235,11 +235,22 @@ uint32_t la_stream_res_max_blocks(const LaGeom &geo, uint32_t feat, uint32_t n, 
     return (uint32_t)std::max(0, safe) * cus;
 }
 
+// 32-bit keys, Fit + Balanced classes without a strategy, unsharded, at most 32 pods a window (a
+// window's inherited and new slots share the 64 slot lanes), and a class and selector geometry with
+// a uniform-window instantiation (res_uniform_class, qs_kernels.hpp: the same function picks the
+// kernel at the launch and in the residency check)
+bool la_stream_res_takes_uniform(const LaGeom &geo, uint32_t feat, uint32_t W) {
+    return geo.k32 && W == 1 && geo.K <= 32 && res_uniform_class(feat, geo.E);
+}
+
 hipError_t launch_la_stream_res(const DevTable &t, const void *pods, const DPodX *podx, const DevCfg &c, uint32_t P,
                                 const LaGeom &geo, uint64_t *lists0, uint64_t *clists0, uint32_t lwords,
                                 uint32_t cwords, uint4 *npart, NormInfo *norm, uint32_t *stat, unsigned long long *nfall,
                                 int32_t *on, uint64_t *ok, uint64_t *st, void *ctl, uint32_t sel_blocks, uint64_t *rdiag,
-                                const ResShard &rsh, hipStream_t stream) {
+                                const ResShard &rsh0, hipStream_t stream, const uint32_t *uni) {
+    // the uniform-window bitmap rides to the kernel in the launch's ResShard
+    ResShard rsh = rsh0;
+    rsh.uni = la_stream_res_takes_uniform(geo, c.feat, rsh0.W) ? uni : nullptr;
     if (geo.G == 0 || (uint64_t)t.n * (t.wrows ? sizeof(DRowW) : sizeof(DRow)) >= (1ull << 31))
         return hipErrorInvalidValue;
     if (c.feat & kFeatStrat)

@@ -2513,6 +2513,19 @@ constexpr uint32_t kResNormK = 32;  // window pods whose NORM records are staged
 // Fit + Balanced (+ext) profiles: stream pods whose list entries / candidate rows sit in the LDS
 // rings of waves 4 (entries) and 5 (rows), indexed by stream pod modulo kResRing
 constexpr uint32_t kResRing = 4;
+// rungs per lane and round of a uniform window (6 is what wave D packs into 64 bits)
+constexpr uint32_t kResUniR = 6;
+// Which (feature class, selector geometry E) pairs have a uniform-window instantiation of
+// k_la_stream_res: the ring classes without a strategy, E <= kResUniMaxE.  The ONE statement of it:
+// la_stream_res_f's launches, la_stream_res_per_cu's residency check and the host-side
+// la_stream_res_takes_uniform all ask this function.  The E bound is reasoning, not a measurement:
+// la_stream_res_plan takes E > 5 only for tables too large for chunks of 5 x 512 nodes (config 3's
+// 50,000 nodes run E = 7), where the selectors and not the resolver bound a window (§5), so the
+// path is expected to gain nothing there; it was never instantiated or timed at E > 5.
+constexpr uint32_t kResUniMaxE = 5;
+constexpr bool res_uniform_class(uint32_t feat, uint32_t E) {
+    return (feat & (kFeatNorm | kFeatStrat)) == 0 && E <= kResUniMaxE;
+}
 constexpr uint32_t kResTStride = 65;
 constexpr size_t kResLdsMax = 96 * 1024;
 constexpr uint32_t kResSgprMax = 112;  // bound on the resident kernels' sgpr_count (checked: tools/kres.sh)  // dynamic LDS of the resident launch (gfx950: up to 160 KiB per workgroup)  // slot statics [pod][lane] rows, padded: both access patterns conflict-free
@@ -2634,14 +2647,19 @@ __device__ __forceinline__ uint64_t res_rescan_wait(const uint64_t *red_k) {
     return ks;
 }
 
-template <uint32_t F, bool K32>
+// UNI: the instantiation that also resolves uniform windows (§4.1h).  A kernel of its own: with the
+// uniform blocks compiled in, the register allocation of the whole kernel shifts, selectors included
+// (config 3: +5 % with the path switched off; profiles/r10_uniform_ab.txt §2), so every launch
+// without a bitmap runs the kernel without them.
+template <uint32_t F, bool K32, bool UNI = false>
 __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable &t, const PodT<F> *__restrict__ pods,
                                                    const DevCfg &c, uint32_t P, uint32_t K, uint32_t nwin,
                                                    const uint64_t *lists0, uint32_t lwords,
                                                    int32_t *__restrict__ out_node, uint64_t *__restrict__ out_key,
                                                    uint64_t *__restrict__ stamps, ResCtl *ctl, uint64_t *rdiag,
                                                    const DPodX *__restrict__ podx, const NormInfo *norm0,
-                                                   const uint32_t *stat0, unsigned long long *nfall) {
+                                                   const uint32_t *stat0, unsigned long long *nfall,
+                                                   const uint32_t *__restrict__ uni) {
     constexpr bool NORM = (F & kFeatNorm) != 0;
     // R32 (the ring form with 32-bit keys, qs_key32.hpp): every key of the pipeline — list entries in
     // ringE, C1, keyC, the score halves in keyA / keyB, the published winner, the per-pod result — is
@@ -2715,6 +2733,41 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
     RowT<F>(*ringR)[64] = (RowT<F>(*)[64])rbase; rbase += kResRing * 64 * sizeof(RowT<F>);
     int4(*ringX)[64] = (int4(*)[64])rbase; rbase += kResRing * 64 * sizeof(int4);
     uint32_t *late = (uint32_t *)rbase;
+    // UNIFORM WINDOWS (R32): a window whose pod records are identical (the host's
+    // bitmap `uni`) is resolved from pod 0's list alone, in rounds of two barriers instead of one
+    // barrier per pod.  Its arrays lie over stage / stagex, which the ring classes never use: the
+    // rows of the window's new slots (C -> A/B at the window end), the slot lanes' and the candidate
+    // lanes' ladders (rung k = tv of the lane's key with k more pods of the window on its node), wave D's
+    // per-lane count deltas of a round, its scratch for the new slots' nodes, the next undecided
+    // pod (every wave reads it after a round's second barrier) and the number of new slots.
+    constexpr uint32_t UR = kResUniR;
+    static_assert(UR >= 2 && UR % 2 == 0, "waves A and B write half of a slot ladder each");
+    static_assert(UR * 10 <= 64, "wave D packs a ladder's rungs (tv < 2^10, qs_key32.hpp) into 64 bits");
+    static_assert(32 * (sizeof(RowT<F>) + 16) + 2 * UR * 256 + 3 * 256 + 16 <= 2 * 64 * (sizeof(RowT<F>) + 16),
+                  "the uniform-window arrays fit in stage / stagex");
+    char *ubase = (char *)stage;
+    RowT<F> *unewR = (RowT<F> *)ubase; ubase += 32 * sizeof(RowT<F>);
+    int4 *unewX = (int4 *)ubase; ubase += 32 * sizeof(int4);
+    uint32_t(*uladS)[64] = (uint32_t(*)[64])ubase; ubase += UR * 256;
+    uint32_t(*uladC)[64] = (uint32_t(*)[64])ubase; ubase += UR * 256;
+    uint32_t *udS = (uint32_t *)ubase; ubase += 256;
+    uint32_t *udC = (uint32_t *)ubase; ubase += 256;
+    uint32_t *utmp = (uint32_t *)ubase; ubase += 256;
+    uint32_t *unext = (uint32_t *)ubase;
+    uint32_t *unew = unext + 1;
+    // every wave reads the same flag and takes the same branch, so the barrier counts stay equal
+    constexpr bool R32U = R32 && UNI;
+    auto uniw = [&](uint32_t w) -> bool { return R32U && uni && ((uni[w >> 5] >> (w & 31)) & 1u) != 0u; };
+    // the waves that only keep the barrier count in a uniform window: two barriers per round, until
+    // wave D's next undecided pod is the window's end (at most kend rounds: each resolves a pod)
+    auto uni_follow = [&](uint32_t kend) {
+        do {
+            __syncthreads();  // U1
+            __syncthreads();  // U2
+        } while (*unext < kend);
+    };
+    (void)unewR; (void)unewX; (void)uladS; (void)uladC; (void)udS; (void)udC; (void)utmp; (void)unew;
+    (void)uniw; (void)uni_follow;
     const ResPub none{0, 0xFFFFFFFFu, -1, -1, 0, {0, 0}};
     // R32: the published winner is 16 bytes in pub's place (waves A / B never read the node)
     ResPub32 *pub32 = (ResPub32 *)pub;
@@ -2730,6 +2783,9 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
     // [0] last step's barrier -> bookkeeping done, [1] -> B2, [2] -> B3, [3] -> B1, [4] -> pod 0 decided
     // [5] B3 -> B1 without the B1 wait (waves A and C: their [0])
     uint64_t bseg_[6] = {0, 0, 0, 0, 0, 0}, bt_ = 0;
+    // QS_RES_DIAG, wave D: uniform windows, their rounds, and their time from B1 to the window end
+    uint64_t utime_ = 0;
+    uint32_t uwin_ = 0, urounds_ = 0;
     auto bmark = [&](int k) {
         if (rdiag) {
             const uint64_t t_ = __builtin_amdgcn_s_memrealtime();
@@ -2790,12 +2846,98 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             uint64_t res_key = 0, res_stamp = 0;
             ResPub pv = none;
             bool stopped = false;  // NORM: a rescan ran in this window
+            const bool uw = uniw(w);  // (read here, before B1: off the window's critical chain)
             if (NORM) __syncthreads();  // B0
             if (w > 0) bmark(5);
             __syncthreads();  // B1
             if (w > 0) bmark(3);
             if (rdiag && lane == 0) store_coh_u64(&rdiag[15], __builtin_amdgcn_s_memrealtime());
-            for (uint32_t i = 0; i < kend; ++i) {
+            if constexpr (R32U) {
+                if (uw) {
+                    // ---- uniform window: pod after pod from the ladders, no barrier between pods ----
+                    const uint64_t tu0 = rdiag ? __builtin_amdgcn_s_memrealtime() : 0ull;
+                    const uint32_t clow = C1[1][lane] & kK32NodeMask;  // this lane's candidate (C, before B1)
+                    uint32_t i = 0, cct = 0;  // cct: pods this lane's candidate took in the window
+                    // a round resolves at least one pod, so the window takes at most kend rounds
+                    while (i < kend) {
+                        __syncthreads();  // U1: the round's rungs are written
+                        // a ladder in one register pair: rung k's tv (10 bits, 0 = infeasible) at bit
+                        // 10 k, so taking a rung is one shift (every VALU instruction of this loop
+                        // is on the window's critical chain)
+                        uint64_t sl = 0, cl = 0;
+#pragma unroll
+                        for (uint32_t k = 0; k < UR; ++k) {
+                            sl |= (uint64_t)uladS[k][lane] << (10 * k);
+                            cl |= (uint64_t)uladC[k][lane] << (10 * k);
+                        }
+                        uint32_t ls = UR, lc = UR, ds = 0, dc = 0;  // rungs left, pods taken this round
+                        for (;;) {
+                            const uint32_t st = (uint32_t)sl & 1023u, ct = (uint32_t)cl & 1023u;
+                            const uint32_t sk = st ? (k32_score(st) | dlow) : 0u;
+                            const uint32_t ck = ct ? (k32_score(ct) | clow) : 0u;
+                            const uint32_t m = wave_max_u32_dpp(sk > ck ? sk : ck);
+                            if (m == 0u) {  // the state stays as it is: every later pod of the window fails too
+                                if ((uint32_t)lane >= i) {
+                                    res_k32 = 0u;
+                                    if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
+                                }
+                                i = kend;
+                                break;
+                            }
+                            if ((uint32_t)lane == i) {
+                                res_k32 = m;
+                                if (stamps) res_stamp = __builtin_amdgcn_s_memrealtime();
+                            }
+                            ++i;
+                            // the owner: a slot lane is found first (a node is never in both sets)
+                            const uint64_t own_s = __ballot(sk == m);
+                            uint32_t left;
+                            if (own_s) {
+                                const int ol = (int)__builtin_ctzll(own_s);
+                                if (lane == ol) {
+                                    sl >>= 10;
+                                    --ls;
+                                    ++ds;
+                                }
+                                left = (uint32_t)__builtin_amdgcn_readlane((int)ls, ol);
+                            } else {
+                                const int ol = (int)__builtin_ctzll(__ballot(ck == m));
+                                if (lane == ol) {
+                                    cl >>= 10;
+                                    --lc;
+                                    ++dc;
+                                }
+                                left = (uint32_t)__builtin_amdgcn_readlane((int)lc, ol);
+                            }
+                            // the owner's ladder is used up: its next key is unknown, the round ends
+                            if (left == 0u || i >= kend) break;
+                        }
+                        udS[lane] = ds;
+                        udC[lane] = dc;
+                        if (lane == 0) *unext = i;
+                        won |= ds > 0u;
+                        cct += dc;
+                        ++urounds_;
+                        __syncthreads();  // U2: the deltas and the next pod are published
+                    }
+                    // window end: the candidate lanes that took a pod become slots nd ... in lane order
+                    // (at most K <= 32 inherited slots and K new ones)
+                    const uint64_t nm = __ballot(cct > 0u);
+                    if (cct > 0u) utmp[nd + (uint32_t)__popcll(nm & ((1ull << lane) - 1ull))] = clow;
+                    __builtin_amdgcn_wave_barrier();
+                    const uint32_t nnew = (uint32_t)__popcll(nm);
+                    if ((uint32_t)lane >= nd && (uint32_t)lane < nd + nnew) {
+                        dlow = utmp[lane];
+                        won = true;
+                    }
+                    nd += nnew;
+                    if (rdiag) {
+                        utime_ += __builtin_amdgcn_s_memrealtime() - tu0;
+                        ++uwin_;
+                    }
+                }
+            }
+            for (uint32_t i = 0, ke = uw ? 0u : kend; i < ke; ++i) {
                 if constexpr (R32) {
                     // 32-bit keys end to end: A / B hand over score halves, the slot's node half
                     // (dlow) is or-ed in, the maximum itself names the owner and the source lane
@@ -3094,14 +3236,52 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 return r;
             };
             if (NORM) __syncthreads();  // B0 (the window's NormInfo is in LDS)
-            if (wv == 1 && nd > 0)  // pod 0, inherited slots
+            bool uw = false;
+            if constexpr (R32U) uw = uniw(w);
+            if (wv == 1 && nd > 0 && !uw)  // pod 0, inherited slots
                 keyA[1][lane] = slot_key(S, SX, wp[0], podn(0), NORM ? Tcur[lane] : 0u);
             if (w > 0) bmark(0);
             __syncthreads();  // B1
             const uint32_t isig = 0;  // the step that signals done for the previous window
+            if constexpr (R32U) {
+                if (uw) {
+                    // ---- uniform window: half of every slot lane's ladder per round (A the lower
+                    // rungs, B the upper ones), then the round's deltas into the slot rows ----
+                    const PodT<F> p0 = wp[0];
+                    if (wv == 1 && pend) {  // (the general path's step isig)
+                        drain_stores();
+                        if (lane == 0) __hip_atomic_store((gu32 *)&ctl->done, pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        pend = 0;
+                    }
+                    // (a ladder scores rows up to UR pods past a node's last feasible state, where the
+                    // int32 columns may wrap: ensure_layout leaves headroom for ONE pod.  fits() reads
+                    // np / rc / rm, which cannot wrap at a node's first infeasible rung, and no later
+                    // rung is read before that one is taken, which it never is: a wrapped score is
+                    // always masked to 0, here and in wave C's ladder)
+                    constexpr uint32_t H = UR / 2;
+                    const uint32_t k0 = wv == 2 ? H : 0u;
+                    const bool act = (uint32_t)lane < nd;
+                    for (;;) {  // (at most kend rounds, see wave D)
+                        RowT<F> r = S;
+                        RowX x = SX;
+                        reserve_n(r, x, p0, (int)k0);
+#pragma unroll
+                        for (uint32_t k = 0; k < H; ++k) {
+                            const bool f = feasible<F>(r, x, p0, px);
+                            const uint32_t tot = fit_bal_total<F, FA>(r, x, p0, cv);
+                            uladS[k0 + k][lane] = (act && f) ? tot + 1 : 0u;  // (tv; wave D packs the ladder)
+                            reserve(r, x, p0, +1);
+                        }
+                        __syncthreads();  // U1
+                        __syncthreads();  // U2
+                        reserve_n(S, SX, p0, (int)udS[lane]);
+                        if (*unext >= kend) break;
+                    }
+                }
+            }
             PodT<F> pprev = wp[0], pcur = wp[0];  // pods i-1 and i (pod i+1's record is read each step)
             PodN pnx = podn(1);                   // NORM: pod i+1's record at step i
-            for (uint32_t i = 0; i < kend; ++i) {
+            for (uint32_t i = 0, ke = uw ? 0u : kend; i < ke; ++i) {
                 QS_RSTAMP_BEGIN()
                 const int par = i & 1, pp = par ^ 1;
                 ResPub pv = rpub(pp);
@@ -3142,8 +3322,21 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
                 __syncthreads();
             }
             if (NORM && rpub((kend - 1) & 1).slot == -2) rescan_ab(kend - 1, w & 1);
-            apply(rpub((kend - 1) & 1), (kend - 1) & 1, pprev, s0 + kend - 1);
+            if (!uw) apply(rpub((kend - 1) & 1), (kend - 1) & 1, pprev, s0 + kend - 1);
             __syncthreads();  // B2 (D's slot ranks and nodes)
+            if constexpr (R32U) {
+                if (uw) {  // the uniform window's new slots: rows with their pods applied, from wave C
+                    const uint32_t nn = *unew;
+                    if ((uint32_t)lane >= nd && (uint32_t)lane < nd + nn) {
+                        S = unewR[(uint32_t)lane - nd];
+                        if (F & kFeatExt) {
+                            const int4 e = unewX[(uint32_t)lane - nd];
+                            SX.ae0 = e.x; SX.re0 = e.y; SX.ae1 = e.z; SX.re1 = e.w;
+                        }
+                    }
+                    nd += nn;
+                }
+            }
             const uint32_t rk = xrank[lane];
             const bool keep = (uint32_t)lane < nd && rk != 0xFFFFFFFFu;
             if (wv == 1 && keep) {
@@ -3452,10 +3645,52 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             const KT e0 = ringE[s0 % kResRing][lane];
             c1 = (e0 != 0 && !dirty_bit(e0)) ? e0 : (KT)0;
             C1[1][lane] = c1;
+            const bool uw = uniw(w);  // (before B1)
             if (w > 0) bmark(0);
             __syncthreads();  // B1
+            if constexpr (R32U) {
+                if (uw) {
+                    // ---- uniform window: every candidate lane's ladder per round from the candidate's
+                    // row and the pods the lane took so far; at the end the lanes that took a pod hand
+                    // their rows to A/B as the window's new slots, in lane order ----
+                    const PodT<F> p0 = wp[0];
+                    const RowT<F> r0 = ringR[s0 % kResRing][lane];
+                    RowX x0{};
+                    if (F & kFeatExt) {
+                        const int4 e = ringX[s0 % kResRing][lane];
+                        x0.ae0 = e.x; x0.re0 = e.y; x0.ae1 = e.z; x0.re1 = e.w;
+                    }
+                    uint32_t ct = 0;
+                    for (;;) {  // (at most kend rounds, see wave D)
+                        RowT<F> r = r0;
+                        RowX x = x0;
+                        reserve_n(r, x, p0, (int)ct);
+#pragma unroll
+                        for (uint32_t k = 0; k < UR; ++k) {
+                            const bool f = feasible<F>(r, x, p0, px);
+                            const uint32_t tot = fit_bal_total<F, FA>(r, x, p0, cv);
+                            uladC[k][lane] = (c1 != 0 && f) ? tot + 1 : 0u;  // (tv; D holds the node half)
+                            reserve(r, x, p0, +1);
+                        }
+                        __syncthreads();  // U1
+                        __syncthreads();  // U2
+                        ct += udC[lane];
+                        if (*unext >= kend) break;
+                    }
+                    const uint64_t nm = __ballot(ct > 0u);
+                    if (ct > 0u) {
+                        const uint32_t rk = (uint32_t)__popcll(nm & ((1ull << lane) - 1ull));
+                        RowT<F> r = r0;
+                        RowX x = x0;
+                        reserve_n(r, x, p0, (int)ct);
+                        unewR[rk] = r;
+                        if (F & kFeatExt) unewX[rk] = make_int4(x.ae0, x.re0, x.ae1, x.re1);
+                    }
+                    if (lane == 0) *unew = (uint32_t)__popcll(nm);
+                }
+            }
             PodT<F> pcur = wp[0];  // pod i's record (pod i+1's is read each step)
-            for (uint32_t i = 0; i < kend; ++i) {
+            for (uint32_t i = 0, ke = uw ? 0u : kend; i < ke; ++i) {
                 QS_RSTAMP_BEGIN()
                 const uint32_t g = s0 + i;
                 const int par = i & 1;
@@ -3527,8 +3762,13 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             const uint32_t ic = pfw ? kend - 3 : kend - 1;  // the step that decides the next window's path
             bool lt = hasnext;
             uint32_t rdyv = 0;
+            const bool uw = uniw(w);  // (before B1)
             __syncthreads();  // B1
-            for (uint32_t i = 0; i < kend; ++i) {
+            if (uw) {  // nothing prefetched: C's fallback fetches the next window's first entries
+                uni_follow(kend);
+                if (lane == 0) *late = 1u;
+            }
+            for (uint32_t i = 0, ke = uw ? 0u : kend; i < ke; ++i) {
                 const uint32_t g = s0 + i;
                 if (!(skip && i == 0)) ringE[(g + 2) % kResRing][lane] = kconv(ein);  // (R32: converted here)
                 if (i == ic) {
@@ -3560,8 +3800,10 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             const uint32_t s0 = w * K, kend = min(K, P - s0);
             const bool hasnext = w + 1 < nwin;
             const bool pfw = hasnext && kend >= 6;
+            const bool uw = uniw(w);  // (before B1)
             __syncthreads();  // B1
-            for (uint32_t i = 0; i < kend; ++i) {
+            if (uw) uni_follow(kend);
+            for (uint32_t i = 0, ke = uw ? 0u : kend; i < ke; ++i) {
                 const uint32_t g = s0 + i;
                 const bool go = i + 1 < kend || (pfw ? *late == 0u : !hasnext);
                 if (go) {
@@ -3714,6 +3956,18 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
             ndi = (uint32_t)__popcll(__ballot(xrank[lane] != 0xFFFFFFFFu));
             __syncthreads();  // B3
         }
+    } else {
+        // ---- waves 6-7 (RING; waves 4-5 fill the entry / row rings): the barrier count only ----
+        for (uint32_t w = 0; w < nwin; ++w) {
+            const uint32_t kend = min(K, P - w * K);
+            const bool uw = uniw(w);  // (before B1)
+            __syncthreads();  // B1
+            if (uw) uni_follow(kend);
+            else
+                for (uint32_t i = 0; i < kend; ++i) __syncthreads();
+            __syncthreads();  // B2
+            __syncthreads();  // B3
+        }
     }
     if (kResDiag && rdiag && lane == 0 && wv < 4) {
         rdiag[8 + wv] = busy_;
@@ -3725,12 +3979,13 @@ __device__ __forceinline__ void la_resolve4_stream(uint32_t *lds, const DevTable
     if (rdiag && lane == 0 && wv == 0)
         for (int k = 0; k < 5; ++k) rdiag[27 + k] = bseg_[k];
     if (rdiag && lane == 0 && wv == 0) rdiag[38] = bseg_[5];
+    if (rdiag && lane == 0 && wv == 0) { rdiag[40] = utime_; rdiag[41] = uwin_; rdiag[42] = urounds_; }
     if (rdiag && lane == 0 && (wv == 1 || wv == 3)) rdiag[wv == 1 ? 37 : 36] = bseg_[0];
 }
 #undef QS_RSTAMP_BEGIN
 #undef QS_RSTAMP_END
 
-template <uint32_t F, int E, int E2, bool K32>
+template <uint32_t F, int E, int E2, bool K32, bool UNI = false>
 __global__ __launch_bounds__(kResBS) void k_la_stream_res(DevTable t, const PodT<F> *__restrict__ pods, DevCfg c,
                                                        uint32_t P, uint32_t K, uint32_t G, uint32_t L,
                                                        uint32_t chunk, uint32_t nwin, uint64_t *lists0,
@@ -3751,16 +4006,17 @@ __global__ __launch_bounds__(kResBS) void k_la_stream_res(DevTable t, const PodT
             __hip_atomic_store(reinterpret_cast<uint64_t *>(rsh.peers[r] + rsh.hello) + rsh.rank, rsh.seq,
                                __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    if ((F & kFeatNorm) == 0 && threadIdx.x >= 384) {
-        // waves 6-7 (waves 4-5 fill the entry / row rings): the same barrier count (1 + per window kend + 3)
+    if (!UNI && (F & kFeatNorm) == 0 && threadIdx.x >= 384) {
+        // waves 6-7 (waves 4-5 fill the entry / row rings): the same barrier count (1 + per window kend + 3);
+        // UNI: inside la_resolve4_stream, where they follow a uniform window's rounds
         __syncthreads();
         for (uint32_t w = 0; w < nwin; ++w)
             for (uint32_t j = 0, nb = min(K, P - w * K) + 3; j < nb; ++j) __syncthreads();
         return;
     }
     const uint64_t t0 = rdiag ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    la_resolve4_stream<F, K32>(lds, t, pods, c, P, K, nwin, lists0, lwords, out_node, out_key, stamps, ctl, rdiag,
-                               podx, norm0, stat0, nfall);
+    la_resolve4_stream<F, K32, UNI>(lds, t, pods, c, P, K, nwin, lists0, lwords, out_node, out_key, stamps, ctl, rdiag,
+                               podx, norm0, stat0, nfall, rsh.uni);
     if (rdiag && threadIdx.x == 0) { rdiag[1] = __builtin_amdgcn_s_memrealtime() - t0; rdiag[3] = nwin; }
 }
 
@@ -3791,8 +4047,18 @@ static hipError_t la_stream_res_f(const DevTable &t, const void *pods, const DPo
     const dim3 grid(1 + sel_blocks);
     const PodT<F> *pp = (const PodT<F> *)pods;
     ResCtl *rc = (ResCtl *)ctl;
+// the uniform-window instantiations: 32-bit keys and res_uniform_class (above)
 #define QS_RESK(EE, EE2, KK)                                                                                          \
     do {                                                                                                              \
+    if constexpr (KK && res_uniform_class(F, EE)) {                                                                  \
+        if (rsh.uni) {                                                                                                \
+            if (hipError_t ea = res_lds_attr((const void *)k_la_stream_res<F, EE, EE2, true, true>, lds4); ea != hipSuccess) return ea; \
+            hipLaunchKernelGGL((k_la_stream_res<F, EE, EE2, true, true>), grid, dim3(kResBS), lds4, stream, t, pp, c, P, K, G, L, \
+                               geo.chunk, nwin, lists0, clists0, lwords, cwords, on, ok, st, rc, rdiag, podx, npart0, norm0, \
+                               stat0, nfall, rsh);                                                                    \
+            break;                                                                                                    \
+        }                                                                                                             \
+    }                                                                                                                 \
     if (hipError_t ea = res_lds_attr((const void *)k_la_stream_res<F, EE, EE2, KK>, lds4); ea != hipSuccess) return ea; \
     hipLaunchKernelGGL((k_la_stream_res<F, EE, EE2, KK>), grid, dim3(kResBS), lds4, stream, t, pp, c, P, K, G, L,       \
                        geo.chunk, nwin, lists0, clists0, lwords, cwords, on, ok, st, rc, rdiag, podx, npart0, norm0,   \
@@ -3822,22 +4088,37 @@ template <uint32_t F>
 static int la_stream_res_per_cu(const LaGeom &geo, uint32_t n) {
     const size_t lds4 = res_stream_lds_bytes<F>(n, geo.k32 != 0);
     const void *fn = nullptr;
-#define QS_RESP(EE, KK) \
-    if (geo.E == EE && geo.e2 == 1 && (geo.k32 != 0) == KK) fn = (const void *)k_la_stream_res<F, EE, 1, KK>;
+    const void *fnu = nullptr;  // the uniform-window instantiation a launch with a bitmap would run
+// (EE, EE2, KK) as la_stream_res_f's QS_RESK launches them, the uniform-window twin by the same test
+#define QS_RESPK(EE, EE2, KK) \
+    if (geo.E == EE && geo.e2 == EE2 && (geo.k32 != 0) == KK) { \
+        fn = (const void *)k_la_stream_res<F, EE, EE2, KK>; \
+        if constexpr (KK && res_uniform_class(F, EE)) fnu = (const void *)k_la_stream_res<F, EE, EE2, true, true>; \
+    }
+#define QS_RESP(EE, KK) QS_RESPK(EE, 1, KK)
     QS_RESP(3, true) QS_RESP(3, false) QS_RESP(5, true) QS_RESP(5, false) QS_RESP(7, true) QS_RESP(7, false)
     QS_RESP(8, true) QS_RESP(8, false) QS_RESP(16, true) QS_RESP(16, false)
 #undef QS_RESP
     if constexpr ((F & kFeatNorm) == 0) {
-#define QS_RESP2(EE, KK) \
-        if (geo.E == EE && geo.e2 == 2 && (geo.k32 != 0) == KK) fn = (const void *)k_la_stream_res<F, EE, 2, KK>;
+#define QS_RESP2(EE, KK) QS_RESPK(EE, 2, KK)
         QS_RESP2(5, true) QS_RESP2(5, false) QS_RESP2(7, true) QS_RESP2(7, false) QS_RESP2(8, true) QS_RESP2(8, false) QS_RESP2(16, true) QS_RESP2(16, false)
 #undef QS_RESP2
     }
+#undef QS_RESPK
     int per = 0;
     if (!fn || res_lds_attr(fn, lds4) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, kResBS, lds4) != hipSuccess) {
         (void)hipGetLastError();
         return 0;
+    }
+    if (fnu) {  // (either kernel may run: every workgroup of the launch must be resident with both)
+        int peru = 0;
+        if (res_lds_attr(fnu, lds4) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&peru, fnu, kResBS, lds4) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        per = peru < per ? peru : per;
     }
     return per;
 }

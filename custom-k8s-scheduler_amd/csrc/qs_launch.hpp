@@ -120,16 +120,25 @@ struct ResShard {
     char *const *peers;
     uint64_t hello, flags, lists;
     uint64_t nflags, norm;
+    // set by launch_la_stream_res from its `uni` argument (callers leave it null)
+    const uint32_t *uni;
 };
 // Normalizing profiles (TaintToleration / NodeAffinity) also pass the pod extension records (podx),
 // npart (2 x K x G uint4 partial maxima), norm (2 x 64 NormInfo), stat (2 x K x 128 u32 entry
 // statics, res_stream_stat_words) and nfall ({rescans, windows with a rescan}); they need K <= 32
 // and sel_blocks >= K * G.
+// uni: bitmap of the windows (of geo.K pods) whose device pod records are identical, or null.  The
+// ring classes with 32-bit keys (Fit + Balanced, ext, wide, configurable resources; unsharded) resolve
+// those windows without a barrier per pod; every other instantiation ignores it.
+// Whether a launch of this geometry, feature set and world size resolves uniform windows (the one
+// place that decides it: launch_la_stream_res drops `uni` otherwise, and the host asks before it
+// builds a bitmap).
+bool la_stream_res_takes_uniform(const LaGeom &geo, uint32_t feat, uint32_t W);
 hipError_t launch_la_stream_res(const DevTable &t, const void *pods, const DPodX *podx, const DevCfg &c, uint32_t P,
                                 const LaGeom &geo, uint64_t *lists0, uint64_t *clists0, uint32_t lwords,
                                 uint32_t cwords, uint4 *npart, NormInfo *norm, uint32_t *stat, unsigned long long *nfall, int32_t *on,
                                 uint64_t *ok, uint64_t *st, void *ctl, uint32_t sel_blocks, uint64_t *rdiag,
-                                const ResShard &rsh, hipStream_t stream);
+                                const ResShard &rsh, hipStream_t stream, const uint32_t *uni = nullptr);
 
 hipError_t launch_la_window(const DevTable &t, const void *pods, const DPodX *podx, uint32_t s0,
                             uint32_t P, const DevCfg &c, const LaGeom &geo, const LaBufs &bufs,

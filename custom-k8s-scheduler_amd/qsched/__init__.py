@@ -326,6 +326,10 @@ class Stream:
         st = QsStats()
         self.s._chk(self.s.lib.qs_stream_run(self.s.ctx, self.h, MODES[mode], ctypes.byref(st)))
         self.stats = st.as_dict()
+        # windows of identical pods the resident launch was given (0: none, or another engine)
+        uw = ctypes.c_uint32(0)
+        self.s._chk(self.s.lib.qs_stream_uniform_windows(self.s.ctx, self.h, ctypes.byref(uw)))
+        self.stats["uniform_windows"] = int(uw.value)
         return self.stats
 
     def results(self):

@@ -169,6 +169,7 @@ _SIGS = {
     "qs_stream_run": (ctypes.c_int, [_P, _P, ctypes.c_int, _P]),
     "qs_stream_results": (ctypes.c_int, [_P, _P, _P, _P]),
     "qs_stream_stamps": (ctypes.c_int, [_P, _P, _P]),
+    "qs_stream_uniform_windows": (ctypes.c_int, [_P, _P, _P]),
     "qs_stream_fit_errors": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint32, _P]),
     "qs_stream_fit_taints": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint32, _P, _P]),
     "qs_stream_free": (ctypes.c_int, [_P, _P]),

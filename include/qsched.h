@@ -317,6 +317,10 @@ QS_API qs_status qs_stream_results(qs_ctx *ctx, qs_stream *s, int32_t *placement
 QS_API qs_status qs_stream_free(qs_ctx *ctx, qs_stream *s);
 /* Per-pod device timestamps (100 MHz s_memrealtime ticks, stream order; record_timestamps = 1). */
 QS_API qs_status qs_stream_stamps(qs_ctx *ctx, qs_stream *s, uint64_t *stamps_p);
+/* How many of the last run's lookahead windows the resident launch was told hold identical pod
+ * records; its ring resolver decides those without a barrier per pod.  0 for every other run, and
+ * with QS_RES_UNIFORM=0. */
+QS_API qs_status qs_stream_uniform_windows(qs_ctx *ctx, qs_stream *s, uint32_t *windows);
 /* FitError diagnosis of an exact stream's unschedulable pods (replaces UP framework/types.go#FitError,
  * Diagnosis.NodeToStatusMap; the "0/N nodes are available: ..." message).  For each requested pod
  * (arrival index) the number of nodes that rejected it for each reason, against the table as it
