@@ -6,6 +6,7 @@
 
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/qsched.h"
@@ -76,6 +77,37 @@ struct Mirror {
     std::vector<uint64_t> th, ts, lb;  // lb [n][2]
     std::vector<int32_t> zone;
     std::vector<uint64_t> gen;
+    // Anti-affinity state recorded while the context tracks it (spec S12; authoritative, the device
+    // arrays DevTable::apps / zcount are rebuilt from it): pods per (app, node), key app << 32 | node,
+    // entries > 0 only, pods per (app, zone), [kMaxApps][kMaxZones] once anything is recorded, and the
+    // recorded pods per node (what qs_node_upsert asks).  resize() keeps all three (qs_nodes_load clears
+    // them).  Zones are < kMaxZones (check_row_values), here as in the kernels (aa_ok).
+    std::unordered_map<uint64_t, int32_t> aa_node;
+    std::vector<int32_t> aa_zone;
+    std::vector<int32_t> aa_pods;
+    void aa_clear() {
+        aa_node.clear();
+        aa_zone.clear();
+        aa_pods.clear();
+    }
+    // One pod of `app` more (sign +1) or fewer (-1) on `node`; returns the node's pods of the app left.
+    int32_t aa_add(uint32_t app, uint32_t node, int sign) {
+        if (aa_zone.empty()) aa_zone.assign((size_t)qs::kMaxApps * qs::kMaxZones, 0);
+        aa_zone[(size_t)app * qs::kMaxZones + (uint32_t)zone[node]] += sign;
+        if (aa_pods.size() < n) aa_pods.resize(n, 0);
+        aa_pods[node] += sign;
+        const uint64_t key = ((uint64_t)app << 32) | node;
+        auto it = aa_node.find(key);
+        if (it == aa_node.end()) it = aa_node.emplace(key, 0).first;
+        const int32_t left = it->second += sign;
+        if (left <= 0) aa_node.erase(it);
+        return left;
+    }
+    bool aa_holds(uint32_t node) const { return node < aa_pods.size() && aa_pods[node] > 0; }
+    int32_t aa_count(uint32_t app, uint32_t node) const {
+        auto it = aa_node.find(((uint64_t)app << 32) | node);
+        return it == aa_node.end() ? 0 : it->second;
+    }
     void resize(uint32_t nn) {
         n = nn;
         zone.assign(nn, 0);
@@ -102,6 +134,7 @@ struct qs_stream {
     bool ran = false;
     int mode_ran = -1;        // qs_mode of the last run
     uint64_t epoch_after = 0;  // the context's table epoch right after the last run (FitError replay)
+    bool aa_ran = false;       // the last run filtered by pod anti-affinity (spec S12: no FitError replay)
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
     // Uniform windows: run0[k] = first stream position of the run of byte-identical
@@ -142,6 +175,7 @@ struct qs_ctx {
     // them while some class scores RequestedToCapacityRatio) and the prepared streams that pin them
     qs_scoring_strategy strat[3] = {};
     qs_host::DevBuf strat_tab;
+    bool aa_track = false;  // required pod anti-affinity on the exact engines / score path (qs_set_pod_anti_affinity, spec S12)
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

@@ -80,8 +80,12 @@ struct DevTable {
 // strategies", S9 "Strategy per QoS class": LeastAllocated, MostAllocated or RequestedToCapacityRatio
 // as the pod record says, pod_sid); the host sets it with kFeatRes | kFeatExt when some pod's class
 // has a strategy other than LeastAllocated.
+// kFeatAA selects required pod anti-affinity on the exact engines and the score path (spec S12): the
+// filter aa_ok below ANDed into feasibility and every placed pod recorded under its app.  The host
+// sets it, with kFeatExt, on every exact stream and qs_score_pod call of a context that tracks
+// anti-affinity (qs_set_pod_anti_affinity); its instantiations live in qs_kernels_aa.inc.
 enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u,
-                           kFeatStrat = 32u };
+                           kFeatStrat = 32u, kFeatAA = 64u };
 
 // pod flags: bits 0-1 QoS, 2-3 the NodeResourcesFit strategy of the pod's QoS class (0 Least, 1 Most,
 // 2 RequestedToCapacityRatio; read by the kFeatStrat scorer only, every other reader masks its own
@@ -90,7 +94,8 @@ enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, k
 __device__ __forceinline__ uint32_t pod_sid(uint32_t flags) { return (flags >> 2) & 3u; }
 __device__ __forceinline__ uint32_t pod_aa(uint32_t flags) { return (flags >> 12) & 3u; }
 __device__ __forceinline__ uint32_t pod_app(uint32_t flags) { return (flags >> 16) & 1023u; }
-// Required anti-affinity of a batched-mode pod against node i (state at batch start).
+// Required anti-affinity of a pod against node i: batched mode against the state at batch start
+// (spec S11), the kFeatAA kernels against the state at the pod's turn (spec S12).
 __device__ __forceinline__ bool aa_ok(const DevTable &t, uint32_t flags, uint32_t i) {
     const uint32_t aa = pod_aa(flags), app = pod_app(flags);
     if (aa == 1u) return !((t.apps[(size_t)(app >> 5) * t.cap + i] >> (app & 31u)) & 1u);

@@ -140,6 +140,22 @@ uint32_t strat_feat(const qs_ctx *c, const qs_pod *pods, uint32_t p) {
     return 0u;
 }
 
+// Feature set of an exact stream or qs_score_pod call on a context that tracks pod anti-affinity
+// (spec S12; qs_kernels_aa.inc): kFeatAA on every one, also a stream without anti-affinity pods, whose
+// pods must still be recorded.  Fit + Balanced (+ ext) LeastAllocated is the default class; everything
+// else runs the general class, the configurable-resource scorers with the per-pod strategy, whose
+// LeastAllocated form over the default lists gives the default scores (as QS_FORCE_RES relies on).
+uint32_t aa_feat(uint32_t feat) {
+    const uint32_t wide = feat & kFeatWide;
+    if ((feat & ~(kFeatWide | kFeatExt)) == 0) return kFeatAA | kFeatExt | wide;
+    const uint32_t norm = (feat & (kFeatTaint | kFeatAffinity)) ? (kFeatTaint | kFeatAffinity) : 0u;
+    return kFeatAA | kFeatExt | kFeatRes | kFeatStrat | wide | norm;
+}
+void aa_check_table(const qs_ctx *c) {
+    if (c->dev_valid && !c->dt.apps)
+        fail(QS_EINVAL, "pod anti-affinity tracking keeps its state for tables up to 2^20 nodes");
+}
+
 DevCfg make_devcfg(const qs_config &c) {
     DevCfg d{};
     int64_t w[5];
@@ -336,9 +352,24 @@ void upload_table(qs_ctx *c) {
         HIPCHK(hipMemcpyAsync(c->dt.masks, masks.data(), n * sizeof(DMask), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->dt.zone, c->m.zone.data(), n * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (c->dt.apps) {  // a (re)loaded table starts with no batched-mode pods placed
-        HIPCHK(hipMemsetAsync(c->dt.apps, 0, (size_t)kAppWords * c->cap * 4, c->stream));
-        HIPCHK(hipMemsetAsync(c->dt.zcount, 0, (size_t)kMaxApps * kMaxZones * 4, c->stream));
+    // a (re)loaded table starts with no pods recorded; what the mirror of a context that tracks pod
+    // anti-affinity holds (spec S12) is rebuilt: a re-layout, or the recovery after a device fault
+    std::vector<uint32_t> aw;
+    if (c->dt.apps) {
+        const bool rebuild = !c->m.aa_node.empty();
+        if (rebuild) {
+            aw.assign((size_t)kAppWords * c->cap, 0u);
+            for (const auto &e : c->m.aa_node) {
+                const uint32_t app = (uint32_t)(e.first >> 32), node = (uint32_t)e.first;
+                if (node < n) aw[(size_t)(app >> 5) * c->cap + node] |= 1u << (app & 31u);
+            }
+            HIPCHK(hipMemcpyAsync(c->dt.apps, aw.data(), aw.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->dt.zcount, c->m.aa_zone.data(), (size_t)kMaxApps * kMaxZones * 4,
+                                  hipMemcpyHostToDevice, c->stream));
+        } else {
+            HIPCHK(hipMemsetAsync(c->dt.apps, 0, (size_t)kAppWords * c->cap * 4, c->stream));
+            HIPCHK(hipMemsetAsync(c->dt.zcount, 0, (size_t)kMaxApps * kMaxZones * 4, c->stream));
+        }
     }
     if (soa) {
         c->soa.ensure(cols.size() * 4);
@@ -694,6 +725,13 @@ bool la_overlap(const qs_ctx *c);
 int pick_engine(const qs_ctx *c, uint32_t n) {
     int e = c->cfg.engine;
     const uint32_t feat = c->dc.feat;
+    if (feat & kFeatAA) {
+        // pod anti-affinity (spec S12): the engines whose kernels carry the filter
+        if (e == QS_ENGINE_LOOKAHEAD || e == QS_ENGINE_ALLREDUCE)
+            fail(QS_EINVAL, "pod anti-affinity tracking runs the PERSISTENT and SCAN engines only: the lookahead "
+                            "lists and the per-pod all-reduce do not carry the anti-affinity filter");
+        if (e == QS_ENGINE_AUTO) e = n <= persistent_max_nodes(feat) ? QS_ENGINE_PERSISTENT : QS_ENGINE_SCAN;
+    }
     if (e == QS_ENGINE_AUTO) {
         if (n > 0 && la_geometry(n, la_window(c), shard_plan(c).W, 2 * la_window(c)).G > 0)
             e = QS_ENGINE_LOOKAHEAD;
@@ -797,7 +835,11 @@ uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, i
         }
     };
     static const char *genv = getenv("QS_GRAPH");
-    if (!kt.on && !(genv && genv[0] == '0')) {
+    // A stream of very many batches (small batch_pods: 100,000 batches of one pod) is enqueued directly:
+    // its graph would be one chain of a few nodes per batch, and instantiating a chain of some 10^5
+    // nodes ended the process with a segmentation fault (10,000 batches instantiate and replay fine)
+    constexpr uint32_t kBatchGraphMax = 8192;
+    if (!kt.on && !(genv && genv[0] == '0') && nb0 <= kBatchGraphMax) {
         std::vector<uint8_t> key;
         auto put = [&](const void *p, size_t nb) { key.insert(key.end(), (const uint8_t *)p, (const uint8_t *)p + nb); };
         const void *ptrs[] = {c->dt.rows, c->dt.wrows, c->dt.apps, bf.lists, bf.clists, ctrl, dp, on, ok};
@@ -1029,6 +1071,26 @@ qs_status qs_get_scoring_strategy_qos(qs_ctx *c, int32_t qos, qs_scoring_strateg
     });
 }
 
+qs_status qs_set_pod_anti_affinity(qs_ctx *c, int32_t on) {
+    return guarded(c, [&] {
+        if (!c->streams.empty())
+            fail(QS_ESTATE, "pod anti-affinity tracking cannot change while prepared streams exist");
+        if (on) {
+            if (c->world > 1 || c->cfg.virtual_shards > 1)
+                fail(QS_EINVAL, "pod anti-affinity tracking runs unsharded (qs_open_shard / virtual_shards > 1)");
+            aa_check_table(c);
+        }
+        c->aa_track = on != 0;  // (the recorded state stays as it is)
+    });
+}
+
+qs_status qs_get_pod_anti_affinity(qs_ctx *c, int32_t *on) {
+    return guarded(c, [&] {
+        if (!on) fail(QS_EINVAL, "null output");
+        *on = c->aa_track ? 1 : 0;
+    });
+}
+
 // (no context: why the calling thread's last qs_open / qs_open_shard failed, or "null context")
 const char *qs_last_error(const qs_ctx *c) {
     if (c) return c->err.c_str();
@@ -1041,6 +1103,7 @@ qs_status qs_nodes_load(qs_ctx *c, const qs_node_soa *nd, uint32_t n) {
         HIPCHK(hipSetDevice(c->device));
         Mirror &m = c->m;
         m.resize(n);
+        m.aa_clear();  // no pod recorded on a new table (spec S12)
         auto get = [](const int64_t *a, size_t i, int64_t d) { return a ? a[i] : d; };
         for (uint32_t i = 0; i < n; i++) {
             m.ac[i] = nd->alloc_cpu[i];
@@ -1114,10 +1177,21 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         one.zone[0] = r->zone;
         one.gen[0] = generation;
         check_row_values(one, 0);
+        if (c->aa_track && idx < m.n && r->zone != m.zone[idx] && m.aa_holds(idx))
+            fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
+                            "cannot change while tracking is on");
         const bool was_zero = idx < m.n && zero_alloc_row(m, idx);
         if (idx == m.n) {  // append one node
+            // (the recorded anti-affinity state is moved aside, not copied with the columns)
+            auto aa_node = std::move(m.aa_node);
+            auto aa_zone = std::move(m.aa_zone);
+            auto aa_pods = std::move(m.aa_pods);
+            m.aa_clear();
             Mirror old = m;
             m.resize(old.n + 1);
+            m.aa_node = std::move(aa_node);
+            m.aa_zone = std::move(aa_zone);
+            m.aa_pods = std::move(aa_pods);
             auto cp = [&](std::vector<int64_t> &d, const std::vector<int64_t> &s) { std::copy(s.begin(), s.end(), d.begin()); };
             cp(m.ac, old.ac); cp(m.am, old.am); cp(m.mp, old.mp); cp(m.rc, old.rc); cp(m.rm, old.rm);
             cp(m.zc, old.zc); cp(m.zm, old.zm); cp(m.np, old.np); cp(m.ae, old.ae); cp(m.re, old.re);
@@ -1148,10 +1222,32 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
         if (node >= c->m.n) fail(QS_EINVAL, "node index out of range");
         check_pod(*p, 0);
         HIPCHK(hipSetDevice(c->device));
+        const uint32_t app = (uint32_t)p->app;
+        if (c->aa_track) {
+            aa_check_table(c);
+            if (sign < 0 && c->m.aa_count(app, node) == 0)
+                fail(QS_EINVAL, "qs_unreserve: no pod of app " + std::to_string(app) + " is recorded on node " +
+                                    std::to_string(node));
+        }
         sync_mirror(c);
         const RowSnap before = snap_row(c->m, node);
         mirror_reserve(c->m, node, *p, sign);
         ++c->table_epoch;
+        // anti-affinity bookkeeping (spec S12), after the row's own path has succeeded: the mirror, then
+        // one small kernel on the context's stream (a table that is not on the device is rebuilt
+        // from the mirror by the next call that needs it)
+        auto aa_record = [&] {
+            if (!c->aa_track) return;
+            const int32_t left = c->m.aa_add(app, node, sign);
+            if (!c->dev_valid) return;
+            hipLaunchKernelGGL(k_aa_apply, dim3(1), dim3(1), 0, c->stream, c->dt, node, app, (int32_t)sign,
+                               left <= 0 ? 1u : 0u);
+            const hipError_t le = hipGetLastError();
+            if (le != hipSuccess) {
+                c->m.aa_add(app, node, -sign);
+                HIPCHK(le);
+            }
+        };
         // any failure from here on (a column driven negative, a layout the stream's growth
         // projection rejects, a device error while pushing the row) leaves the mirror as it was:
         // the caller was told the reservation failed
@@ -1161,7 +1257,14 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
                 // the row changes in place: no device call now — the next qs_score_pod launch writes
                 // it (and scores it from its argument), any other call writes it first
                 if (c->pend != 0xFFFFFFFFu && c->pend != node) flush_pending(c);
+                const uint32_t pend_before = c->pend;
                 c->pend = node;
+                try {
+                    aa_record();
+                } catch (...) {
+                    c->pend = pend_before;
+                    throw;
+                }
                 return;
             }
             flush_pending(c);
@@ -1170,6 +1273,7 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
             const bool old_wide = c->wide;
             ensure_layout(c, p, 1);
             if (was_valid && c->shift == old_shift && c->wide == old_wide) push_row(c, node);
+            aa_record();
         } catch (...) {
             put_row(c->m, node, before);
             throw;
@@ -1371,6 +1475,10 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
     const bool pod_ext = pod->req_ext[0] || pod->req_ext[1];
     dc.feat = feat_of(c->cfg) | (pod_ext ? kFeatExt : 0u) | (c->wide ? kFeatWide | kFeatExt : 0u) |
               res_feat(c->cfg, pod_ext) | strat_feat(c, pod, 1);
+    if (c->aa_track) {  // spec S12: the anti-affinity filter on the score path
+        aa_check_table(c);
+        dc.feat = aa_feat(dc.feat);
+    }
     wts[2] = (dc.feat & kFeatTaint) ? (uint32_t)dc.wtt : 0u;
     wts[3] = (dc.feat & kFeatAffinity) ? (uint32_t)dc.wna : 0u;
     if (n == 0 || !c->dev_valid) {
@@ -1506,10 +1614,16 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         s->ran = false;
         s->mode_ran = -1;
         s->uni_given = 0;
+        s->aa_ran = false;
         ++c->table_epoch;
         if (!c->dev_valid) upload_table(c);  // recovery after a device fault: rebuild from the mirror
         const uint32_t n = c->m.n, P = s->p;
         c->dc.feat = s->feat;
+        // pod anti-affinity (spec S12): every exact stream of a tracking context carries the filter
+        // and records its pods; batched mode filters and records by itself (S11, the same state)
+        const bool aa_exact = c->aa_track && mode == QS_MODE_EXACT;
+        if (c->aa_track) aa_check_table(c);
+        if (aa_exact) c->dc.feat = aa_feat(s->feat);
         const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n);
         int32_t *on = s->d_node.as<int32_t>();
         uint64_t *ok = s->d_key.as<uint64_t>();
@@ -2081,6 +2195,16 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         // keep the host mirror authoritative after every stream (one D2H of the rows, outside
         // the timed region): a later device fault rebuilds the table from it
         sync_mirror(c);
+        if (c->aa_track && P > 0 && n > 0) {
+            // fold the run's placements into the mirror's anti-affinity state (4 P bytes back, outside
+            // wall_s): the mirror stays authoritative for save / restore and the recovery rebuild
+            std::vector<int32_t> node(P);
+            HIPCHK(hipMemcpy(node.data(), s->d_node.p, 4 * (size_t)P, hipMemcpyDeviceToHost));
+            for (uint32_t k = 0; k < P; k++)
+                if (node[k] >= 0 && (uint32_t)node[k] < n)
+                    c->m.aa_add((uint32_t)s->pods[s->order[k]].app, (uint32_t)node[k], +1);
+        }
+        s->aa_ran = aa_exact;
         s->ran = true;
         s->mode_ran = (int)mode;
         s->epoch_after = ++c->table_epoch;
@@ -2221,6 +2345,9 @@ static qs_status fit_errors(qs_ctx *c, qs_stream *s, const uint32_t *pods, uint3
     return guarded(c, [&] {
         if (!s || !s->ran) fail(QS_ESTATE, "stream has not run");
         if (s->mode_ran != QS_MODE_EXACT) fail(QS_EINVAL, "FitError diagnosis covers exact streams");
+        if (s->aa_ran)
+            fail(QS_EINVAL, "FitError diagnosis does not cover streams run with pod anti-affinity tracking (the replay "
+                            "would need the anti-affinity state at every pod's turn)");
         if (s->epoch_after != c->table_epoch) fail(QS_ESTATE, "the node table changed after the stream's run");
         if (mreq && (!pods || !counts)) fail(QS_EINVAL, "null pods / counts");
         const uint32_t P = s->p;

@@ -63,6 +63,9 @@ static uint32_t feat_class(uint32_t feat) {
 hipError_t launch_persistent(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                              const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st,
                              hipStream_t stream) {
+    if (c.feat & kFeatAA)
+        return t.wrows ? aa_wide_persistent(t, pods, podx, P, c, on, ok, st, stream)
+                       : aa_compact_persistent(t, pods, podx, P, c, on, ok, st, stream);
     if (c.feat & kFeatStrat)
         return t.wrows ? strat_wide_persistent(t, pods, podx, P, c, on, ok, st, stream)
                        : strat_compact_persistent(t, pods, podx, P, c, on, ok, st, stream);
@@ -80,6 +83,8 @@ hipError_t launch_persistent(const DevTable &t, const void *pods, const DPodX *p
 }
 
 uint32_t persistent_max_nodes(uint32_t feat) {
+    if (feat & kFeatAA)
+        return (feat & kFeatWide) ? aa_wide_persistent_max_nodes(feat) : aa_compact_persistent_max_nodes(feat);
     if (feat & kFeatStrat)
         return (feat & kFeatWide) ? strat_wide_persistent_max_nodes(feat) : strat_compact_persistent_max_nodes(feat);
     if (feat & kFeatRes)
@@ -102,6 +107,9 @@ hipError_t launch_scan_pod(const DevTable &t, const void *pods, const DPodX *pod
                            const DevCfg &c, void *scratch, int32_t *on, uint64_t *ok, uint64_t *st,
                            uint8_t *feas, int32_t *score, int32_t *total, int part,
                            hipStream_t stream) {
+    if (c.feat & kFeatAA)
+        return t.wrows ? aa_wide_scan_pod(t, pods, podx, s, c, scratch, on, ok, st, feas, score, total, part, stream)
+                       : aa_compact_scan_pod(t, pods, podx, s, c, scratch, on, ok, st, feas, score, total, part, stream);
     if (c.feat & kFeatStrat)
         return t.wrows ? strat_wide_scan_pod(t, pods, podx, s, c, scratch, on, ok, st, feas, score, total, part, stream)
                        : strat_compact_scan_pod(t, pods, podx, s, c, scratch, on, ok, st, feas, score, total, part, stream);
@@ -123,6 +131,9 @@ uint32_t score_pod1_max_nodes() { return kScorePod1Max; }
 size_t score_pod1_pack_bytes(uint32_t n) { return score_pack_bytes(n); }
 hipError_t launch_score_pod1(const DevTable &t, const void *pod, const DPodX *podx, const DevCfg &c, uint8_t *hout,
                              uint64_t *gs, uint64_t seq, uint32_t pidx, const HostRow &prow, hipStream_t stream) {
+    if (c.feat & kFeatAA)
+        return t.wrows ? aa_wide_score_pod1(t, pod, podx, c, hout, gs, seq, pidx, prow, stream)
+                       : aa_compact_score_pod1(t, pod, podx, c, hout, gs, seq, pidx, prow, stream);
     if (c.feat & kFeatStrat)
         return t.wrows ? strat_wide_score_pod1(t, pod, podx, c, hout, gs, seq, pidx, prow, stream)
                        : strat_compact_score_pod1(t, pod, podx, c, hout, gs, seq, pidx, prow, stream);
@@ -153,6 +164,7 @@ hipError_t launch_la_window(const DevTable &t, const void *pods, const DPodX *po
                             uint32_t P, const DevCfg &c, const LaGeom &geo, const LaBufs &bf,
                             int32_t *on, uint64_t *ok, uint64_t *st, uint64_t *diag,
                             hipStream_t stream, int part) {
+    if (c.feat & kFeatAA) return hipErrorInvalidValue;  // no lookahead kernel carries the filter
     if (bf.dprev && geo.waves == 1 && !(c.feat & kFeatNorm)) return hipErrorInvalidValue;
     if ((c.feat & kFeatNorm) && diag && geo.waves != 4) return hipErrorInvalidValue;
     if (c.feat & kFeatStrat)
@@ -251,7 +263,7 @@ hipError_t launch_la_stream_res(const DevTable &t, const void *pods, const DPodX
     // the uniform-window bitmap rides to the kernel in the launch's ResShard
     ResShard rsh = rsh0;
     rsh.uni = la_stream_res_takes_uniform(geo, c.feat, rsh0.W) ? uni : nullptr;
-    if (geo.G == 0 || (uint64_t)t.n * (t.wrows ? sizeof(DRowW) : sizeof(DRow)) >= (1ull << 31))
+    if (geo.G == 0 || (c.feat & kFeatAA) || (uint64_t)t.n * (t.wrows ? sizeof(DRowW) : sizeof(DRow)) >= (1ull << 31))
         return hipErrorInvalidValue;
     if (c.feat & kFeatStrat)
         return (t.wrows ? strat_wide_la_stream_res : strat_compact_la_stream_res)(

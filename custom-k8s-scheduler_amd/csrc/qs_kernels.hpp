@@ -41,6 +41,19 @@ constexpr uint32_t kFeatNorm = kFeatTaint | kFeatAffinity;
 // =============================================================================================
 // PERSISTENT engine
 // =============================================================================================
+// Anti-affinity state of the persistent workgroup (kFeatAA, spec S12) in LDS: per app the zones that
+// hold a pod of it (bit z of zmask[app] set iff zcount[app][z] != 0; 8 KB) and the zone of every node
+// of the table (one byte each), which tells every thread the winner's zone.
+__device__ __forceinline__ uint64_t *aa_lds_zmask() {
+    __shared__ uint64_t zmask[kMaxApps];
+    return zmask;
+}
+template <int N>
+__device__ __forceinline__ uint8_t *aa_lds_zone() {
+    __shared__ uint8_t zl[N];
+    return zl;
+}
+
 template <int NPT, int BS, uint32_t F>
 __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__restrict__ pods,
                                                    const DPodX *__restrict__ podx, uint32_t P,
@@ -60,19 +73,74 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
         if (idx < n) { r[k] = load_row<F>(t, idx); x[k] = load_rowx<F>(t, idx); }
         else { r[k] = empty_row<F>(); x[k] = RowX{0, 0, 0, 0, 0, 0, 0, 0}; }
     }
+    // kFeatAA: the lane's nodes' zones beside the rows, the LDS state, and the previous pod's record
+    // (its app and its winner's zone bit; see the ZONE filter below)
+    [[maybe_unused]] uint32_t zn[NPT];
+    [[maybe_unused]] uint64_t *zmask = nullptr;
+    [[maybe_unused]] uint8_t *zl = nullptr;
+    [[maybe_unused]] uint32_t prev_app = 0;
+    [[maybe_unused]] uint64_t prev_bit = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        zmask = aa_lds_zmask();
+        zl = aa_lds_zone<NPT * BS>();
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const uint32_t idx = tid + k * BS;
+            zn[k] = idx < n ? (uint32_t)t.zone[idx] : 0u;  // (< kMaxZones: the host checks every row, as aa_ok relies on)
+            zl[idx] = (uint8_t)zn[k];
+        }
+        for (uint32_t a = tid; a < kMaxApps; a += BS) {
+            const int4 *q = reinterpret_cast<const int4 *>(t.zcount + a * kMaxZones);
+            uint64_t m = 0;
+#pragma unroll
+            for (int j = 0; j < (int)kMaxZones / 4; ++j) {
+                const int4 v = q[j];
+                const uint64_t b = (uint64_t)(v.x != 0) | ((uint64_t)(v.y != 0) << 1) |
+                                   ((uint64_t)(v.z != 0) << 2) | ((uint64_t)(v.w != 0) << 3);
+                m |= b << (4 * j);
+            }
+            zmask[a] = m;
+        }
+        __syncthreads();
+    }
     PodT<F> pn = pods[0];
     for (uint32_t s = 0; s < P; ++s) {
         const PodT<F> p = pn;
         pn = pods[s + 1 < P ? s + 1 : s];  // prefetch the next pod record (scalar loads)
         DPodX px;
         if (F & kFeatNorm) px = podx[s];
+        // kFeatAA filter (spec S12), bit k = node k of the lane passes.  The pod record is
+        // wave-uniform, so the kind is a scalar branch.  ZONE: one LDS word.  Thread 0 wrote the
+        // previous pod's bit after that pod's barrier, which does not order it before this read by
+        // another wave; every thread knows that pod's app and winner, and ORs the bit in itself
+        // (older bits are a barrier behind).  HOSTNAME: the presence word of the lane's own nodes,
+        // which only this thread ever reads or writes.
+        [[maybe_unused]] uint32_t aam = ~0u;
+        if constexpr ((F & kFeatAA) != 0) {
+            const uint32_t kind = pod_aa(p.flags), app = pod_app(p.flags);
+            if (kind == 2u) {
+                uint64_t zw = __hip_atomic_load(&zmask[app], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                zw |= app == prev_app ? prev_bit : 0ull;
+#pragma unroll
+                for (int k = 0; k < NPT; ++k) aam &= ~((uint32_t)((zw >> zn[k]) & 1ull) << k);
+            } else if (kind == 1u) {
+                const uint32_t *aw = t.apps + (size_t)(app >> 5) * t.cap;
+#pragma unroll
+                for (int k = 0; k < NPT; ++k) {
+                    const uint32_t idx = tid + k * BS;
+                    const uint32_t wd = idx < n ? aw[idx] : 0u;
+                    aam &= ~(((wd >> (app & 31u)) & 1u) << k);
+                }
+            }
+        }
         uint32_t mt = 0, ma = 0;
         double ymt = 0.0, yma = 0.0;
         if (F & kFeatNorm) {  // NormalizeScore maxima over feasible nodes (spec S5)
             uint32_t lt = 0, la = 0;
 #pragma unroll
             for (int k = 0; k < NPT; ++k) {
-                const bool f = feasible<F>(r[k], x[k], p, px);
+                bool f = feasible<F>(r[k], x[k], p, px);
+                if constexpr ((F & kFeatAA) != 0) f &= ((aam >> k) & 1u) != 0;
                 const uint32_t a = f ? taint_raw(x[k], px) : 0u;
                 const uint32_t b = f ? affinity_raw(x[k], p, px) : 0u;
                 lt = a > lt ? a : lt;
@@ -94,7 +162,8 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
         uint64_t best = 0;
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
-            const bool f = feasible<F>(r[k], x[k], p, px);
+            bool f = feasible<F>(r[k], x[k], p, px);
+            if constexpr ((F & kFeatAA) != 0) f &= ((aam >> k) & 1u) != 0;
             const uint32_t tot = node_total<F>(r[k], x[k], p, px, c, mt, ymt, ma, yma, nullptr);
             const uint64_t key = f ? pack_key(tot + 1, tid + k * BS) : 0ull;
             best = key > best ? key : best;
@@ -113,6 +182,30 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
 #pragma unroll
             for (int k = 0; k < NPT; ++k)
                 if (tid + k * BS == win) reserve(r[k], x[k], p, +1);
+        }
+        if constexpr ((F & kFeatAA) != 0) {
+            // record the placed pod under its app, whatever its kind (spec S12): the owning thread
+            // sets the presence bit of its node; thread 0 keeps the zone state, in LDS for the rest
+            // of this stream and in global memory for the launches after it (one workgroup runs
+            // the stream, so nothing here is read by another CU before the kernel ends)
+            const uint32_t app = pod_app(p.flags);
+            prev_app = app;
+            prev_bit = 0;
+            if (ks != 0) {
+                const uint32_t wz = zl[win];
+                prev_bit = 1ull << wz;
+                if (tid == 0) {
+                    const uint64_t old = __hip_atomic_load(&zmask[app], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_store(&zmask[app], old | prev_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    atomicAdd(&t.zcount[app * kMaxZones + wz], 1);
+                }
+#pragma unroll
+                for (int k = 0; k < NPT; ++k)
+                    if (tid + k * BS == win) {
+                        uint32_t *wp = t.apps + (size_t)(app >> 5) * t.cap + win;
+                        *wp = *wp | (1u << (app & 31u));
+                    }
+            }
         }
         if (tid == 0) {
             out_node[s] = ks ? (int32_t)win : -1;
@@ -168,7 +261,9 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
-        if (feasible<F>(r, x, p, px)) {
+        bool f = feasible<F>(r, x, p, px);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if (f) {
             const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
             lt = a > lt ? a : lt;
             la = b > la ? b : la;
@@ -199,9 +294,13 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
-        const bool f = feasible<F>(r, x, p, px);
+        bool f = feasible<F>(r, x, p, px);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
         uint32_t sco[4];
-        const uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma, score_out ? sco : nullptr);
+        // (kFeatAA classes: the scores always go to the local array, which then stays in registers;
+        // the pointer select of the older classes keeps their heavier scorers' array in scratch)
+        const uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma,
+                                           ((F & kFeatAA) != 0 || score_out) ? sco : nullptr);
         const uint64_t key = f ? pack_key(tot + 1, i) : 0ull;
         best = key > best ? key : best;
         if (feas_out) feas_out[i] = f;
@@ -265,9 +364,12 @@ __global__ __launch_bounds__(256) void k_scan_soa(DevTable t, const PodT<F> *__r
             RowX x{};
             if (F & kFeatExt) { x.ae0 = el(kSAe0); x.re0 = el(kSRe0); x.ae1 = el(kSAe1); x.re1 = el(kSRe1); }
             const uint32_t idx = 4 * q + e;
-            const bool f = feasible<F>(r, x, p, px);  // padding rows: max_pods 0 -> infeasible
+            bool f = feasible<F>(r, x, p, px);  // padding rows: max_pods 0 -> infeasible
+            // (the zone column is read for ZONE pods only; padding rows have no zone)
+            if constexpr ((F & kFeatAA) != 0) f = f && idx < t.n && aa_ok(t, p.flags, idx);
             uint32_t sco[4];
-            const uint32_t tot = node_total<F>(r, x, p, px, c, 0, 0.0, 0, 0.0, score_out ? sco : nullptr);
+            const uint32_t tot = node_total<F>(r, x, p, px, c, 0, 0.0, 0, 0.0,
+                                               ((F & kFeatAA) != 0 || score_out) ? sco : nullptr);
             const uint64_t key = f ? pack_key(tot + 1, idx) : 0ull;
             best = key > best ? key : best;
             if (idx < t.n) {
@@ -321,6 +423,13 @@ __global__ __launch_bounds__(256) void k_scan_commit(DevTable t, const PodT<F> *
             t.soa.c[kSZc][w] = r.zc; t.soa.c[kSZm][w] = r.zm;
             t.soa.c[kSNp][w] = r.np;
             if (F & kFeatExt) { t.soa.c[kSRe0][w] = x.re0; t.soa.c[kSRe1][w] = x.re1; }
+        }
+        if constexpr ((F & kFeatAA) != 0) {
+            // record the placed pod under its app (spec S12); the next pod's scan is a later launch
+            const uint32_t app = pod_app(p.flags);
+            uint32_t *wp = t.apps + (size_t)(app >> 5) * t.cap + w;
+            *wp = *wp | (1u << (app & 31u));
+            t.zcount[app * kMaxZones + (uint32_t)t.zone[w]] += 1;
         }
     }
     out_node[s] = ks ? (int32_t)key_node(ks) : -1;
@@ -407,7 +516,9 @@ __global__ __launch_bounds__(1024) void k_score_pod1(DevTable t, PodT<F> p, DPod
             RowT<F> r;
             RowX x;
             row_at(i, r, x);
-            if (feasible<F>(r, x, p, px)) {
+            bool f = feasible<F>(r, x, p, px);
+            if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+            if (f) {
                 const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
                 mt = a > mt ? a : mt;
                 ma = b > ma ? b : ma;
@@ -429,7 +540,8 @@ __global__ __launch_bounds__(1024) void k_score_pod1(DevTable t, PodT<F> p, DPod
         RowT<F> r;
         RowX x;
         row_at(i, r, x);
-        const bool f = feasible<F>(r, x, p, px);
+        bool f = feasible<F>(r, x, p, px);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
         uint32_t sco[4];
         const uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma, sco);
         const uint64_t key = f ? pack_key(tot + 1, i) : 0ull;
@@ -473,7 +585,9 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
             r = load_row<F>(t, i);
             x = load_rowx<F>(t, i);
         }
-        if (feasible<F>(r, x, p, px)) {
+        bool f = feasible<F>(r, x, p, px);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if (f) {
             mt = taint_raw(x, px);
             ma = affinity_raw(x, p, px);
         }
@@ -509,7 +623,8 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
             r = load_row<F>(t, i);
             x = load_rowx<F>(t, i);
         }
-        const bool f = feasible<F>(r, x, p, px);
+        bool f = feasible<F>(r, x, p, px);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
         uint32_t sco[4];
         const uint32_t tot = node_total<F>(r, x, p, px, c, mt, rcp_exact(mt), ma, rcp_exact(ma), sco);
         best = f ? pack_key(tot + 1, i) : 0ull;
@@ -4354,6 +4469,12 @@ static hipError_t persistent_t(const DevTable &t, const void *pods, const DPodX 
 // engine is the fast path at these sizes).  Wide rows carry three f64 memory columns.
 template <uint32_t F>
 static constexpr uint32_t persistent_cap() {
+    // anti-affinity classes (kFeatAA): a zone register per node beside the rows, and no spill at all
+    // (tests/test_antiaffinity_cpu.py reads the code objects): see DESIGN.md §3.4 for the budget
+    if (F & kFeatAA) {
+        if (F & kFeatWide) return (F & kFeatNorm) ? 1024u : 2048u;
+        return (F & (kFeatNorm | kFeatRes)) ? 2048u : 3072u;
+    }
     if (F & kFeatWide) return (F & kFeatNorm) ? 2048u : 5120u;
     return F == 0 ? 6144u : (F == kFeatExt ? 5120u : 2048u);
 }
@@ -4369,9 +4490,13 @@ static hipError_t persistent_f(const DevTable &t, const void *pods, const DPodX 
     if (n <= 256) return persistent_t<1, 256, F>(t, pods, podx, P, c, on, ok, st, stream);
     if (n <= 512) return persistent_t<1, 512, F>(t, pods, podx, P, c, on, ok, st, stream);
     if (n <= 1024) return persistent_t<1, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 2048) return persistent_t<2, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F>() > 1024) {
+        if (n <= 2048) return persistent_t<2, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    }
     if constexpr (persistent_cap<F>() > 2048) {
         if (n <= 3072) return persistent_t<3, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    }
+    if constexpr (persistent_cap<F>() > 3072) {
         if (n <= 4096) return persistent_t<4, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
     }
     if constexpr (persistent_cap<F>() > 4096) {
@@ -4631,5 +4756,20 @@ QS_DECL_RES(res_wide_)
 QS_DECL_RES(strat_compact_)
 QS_DECL_RES(strat_wide_)
 #undef QS_DECL_RES
+// Anti-affinity entry points (kFeatAA, spec S12; qs_kernels_aa.inc, one translation unit per row
+// layout): the PERSISTENT and SCAN engines and the score path only.
+#define QS_DECL_AA(P)                                                                                         \
+    hipError_t P##persistent(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P_,            \
+                             const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st, hipStream_t stream);   \
+    uint32_t P##persistent_max_nodes(uint32_t feat);                                                          \
+    hipError_t P##scan_pod(const DevTable &t, const void *pods, const DPodX *podx, uint32_t s,               \
+                           const DevCfg &c, void *scratch, int32_t *on, uint64_t *ok, uint64_t *st,           \
+                           uint8_t *feas, int32_t *score, int32_t *total, int part, hipStream_t stream);      \
+    hipError_t P##score_pod1(const DevTable &t, const void *pod, const DPodX *podx, const DevCfg &c,         \
+                             uint8_t *hout, uint64_t *gs, uint64_t seq, uint32_t pidx, const HostRow &prow,   \
+                             hipStream_t stream);
+QS_DECL_AA(aa_compact_)
+QS_DECL_AA(aa_wide_)
+#undef QS_DECL_AA
 
 }  // namespace qs

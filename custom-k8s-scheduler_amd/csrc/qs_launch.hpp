@@ -156,5 +156,8 @@ hipError_t launch_batch_claim(const DevTable &t, const void *pods, const uint64_
                               uint64_t *out_key, hipStream_t stream);
 
 __global__ void k_set_row(DevTable t, uint32_t i, HostRow v, uint32_t feat);
+// Reserve (sign +1) / Unreserve (-1) of one pod of `app` on `node` in the anti-affinity state
+// (spec S12): sets the presence bit, or clears it when clear_bit, and moves the (app, zone) count.
+__global__ void k_aa_apply(DevTable t, uint32_t node, uint32_t app, int32_t sign, uint32_t clear_bit);
 
 }  // namespace qs

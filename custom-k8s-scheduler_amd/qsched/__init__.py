@@ -188,6 +188,16 @@ class Scheduler:
         name = {v: k for k, v in STRATEGIES.items()}[int(st.type)]
         return name, [(int(st.shape[i][0]), int(st.shape[i][1])) for i in range(int(st.n_shape))]
 
+    def set_pod_anti_affinity(self, on=True):
+        """qs_set_pod_anti_affinity: required pod anti-affinity (``app`` / ``anti_affinity``) on the
+        exact engines, score_pod and reserve / unreserve (spec S12); off in a new context."""
+        self._chk(self.lib.qs_set_pod_anti_affinity(self.ctx, 1 if on else 0))
+
+    def get_pod_anti_affinity(self) -> bool:
+        on = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_pod_anti_affinity(self.ctx, ctypes.byref(on)))
+        return bool(on.value)
+
     def mailbox_export(self) -> bytes:
         """qs_dist_mailbox_export: this rank's 64-byte mailbox IPC handle (sharded contexts opened
         without an RCCL id)."""

@@ -151,6 +151,8 @@ _SIGS = {
     "qs_set_scoring_strategy": (ctypes.c_int, [_P, _P]),
     "qs_set_scoring_strategy_qos": (ctypes.c_int, [_P, ctypes.c_int32, _P]),
     "qs_get_scoring_strategy_qos": (ctypes.c_int, [_P, ctypes.c_int32, _P]),
+    "qs_set_pod_anti_affinity": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "qs_get_pod_anti_affinity": (ctypes.c_int, [_P, _P]),
     "qs_shape_table": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "qs_close": (ctypes.c_int, [_P]),
     "qs_last_error": (ctypes.c_char_p, [_P]),

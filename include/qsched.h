@@ -69,8 +69,10 @@ typedef enum qs_qos { QS_QOS_BESTEFFORT = 0, QS_QOS_BURSTABLE = 1, QS_QOS_GUARAN
 
 typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
 
-/* Required pod anti-affinity to the pod's own app group (batched mode, spec S11; the subset of
- * UP plugins/interpodaffinity that config 5 uses): none, per node (topologyKey hostname), per zone. */
+/* Required pod anti-affinity to the pod's own app group (the subset of UP plugins/interpodaffinity
+ * that config 5 uses): none, per node (topologyKey hostname), per zone.  QS_MODE_BATCHED always
+ * honours it (spec S11); exact streams, qs_score_pod and qs_reserve / qs_unreserve honour it on a
+ * context that tracks it (qs_set_pod_anti_affinity, spec S12) and ignore it otherwise. */
 typedef enum qs_anti_affinity { QS_AA_NONE = 0, QS_AA_HOSTNAME = 1, QS_AA_ZONE = 2 } qs_anti_affinity;
 
 /* Scoring resources (spec/semantics.md S5 "Scoring resources"): cpu, memory, or one of the table's
@@ -193,8 +195,10 @@ typedef struct qs_pod {
     uint64_t req_terms[QS_MAX_TERMS][2];  /* required node-affinity terms (OR of ANDs) */
     uint64_t pref_terms[QS_MAX_TERMS][2]; /* preferred terms */
     int32_t pref_weight[QS_MAX_TERMS];
-    int32_t app;           /* anti-affinity group (< QS_MAX_APPS) */
-    int32_t anti_affinity; /* qs_anti_affinity: required anti-affinity to the pod's own app */
+    int32_t app;           /* anti-affinity group (< QS_MAX_APPS); with tracking on (spec S12) every
+                              placed pod is recorded under it, whatever its anti_affinity */
+    int32_t anti_affinity; /* qs_anti_affinity: required anti-affinity to the pod's own app (batched
+                              mode; exact mode and the score path with tracking on, else ignored) */
 } qs_pod;
 
 /* One container of a pod spec for qs_pod_from_containers (spec S2/S3). has_* = 0 means missing. */
@@ -278,6 +282,27 @@ QS_API qs_status qs_set_scoring_strategy(qs_ctx *ctx, const qs_scoring_strategy 
  * has another strategy.  qs_get_scoring_strategy_qos returns what is stored for the class. */
 QS_API qs_status qs_set_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, const qs_scoring_strategy *s);
 QS_API qs_status qs_get_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, qs_scoring_strategy *out);
+/* Required pod anti-affinity on the exact engines and the score path (spec S12), per context, off in a
+ * new context (nothing changes anywhere while it is off).  on != 0: every later exact stream and
+ * qs_score_pod call filters HOSTNAME / ZONE pods against the recorded (app, node) / (app, zone) state
+ * (an infeasible node takes no part in the TaintToleration / NodeAffinity maxima), and every pod placed
+ * by an exact or batched stream or by qs_reserve is recorded under its app; qs_unreserve removes one.
+ * The state is that of batched mode on the same context (shared), empty after qs_nodes_load, kept by
+ * qs_table_save / qs_table_restore and rebuilt after a device fault; switching tracking on or off does
+ * not clear it, and nothing is recorded while it is off.  That holds for the host's record, from which
+ * qs_unreserve, the zone rule below and every rebuild of the device state work; a batched stream still
+ * marks the device state with tracking off (S11, as before), so pods it places then filter later pods
+ * until the table is re-laid out or rebuilt, but qs_unreserve does not know them (QS_EINVAL) and a zone
+ * change of their node is not refused.  Switch tracking on before the first stream whose pods should
+ * count.  Exact streams then run QS_ENGINE_PERSISTENT
+ * (tables that fit it) or QS_ENGINE_SCAN; an explicit QS_ENGINE_LOOKAHEAD / QS_ENGINE_ALLREDUCE makes
+ * qs_stream_run return QS_EINVAL, as do qs_stream_fit_errors / qs_stream_fit_taints of a tracked run and
+ * a qs_node_upsert that moves a node holding recorded pods to another zone.  QS_ESTATE while the context
+ * holds prepared streams; QS_EINVAL (switching on) on a sharded context (qs_open_shard, virtual_shards
+ * > 1) or when the loaded table keeps no anti-affinity state (more than 2^20 nodes), and for a null
+ * output pointer. */
+QS_API qs_status qs_set_pod_anti_affinity(qs_ctx *ctx, int32_t on);
+QS_API qs_status qs_get_pod_anti_affinity(qs_ctx *ctx, int32_t *on);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);
@@ -289,13 +314,20 @@ QS_API qs_status qs_node_upsert(qs_ctx *ctx, uint32_t idx, const qs_node_row *ro
 /* Device-side snapshot of the whole node table (checkpoint/resume; bench resets between steps). */
 QS_API qs_status qs_table_save(qs_ctx *ctx);
 QS_API qs_status qs_table_restore(qs_ctx *ctx);
+/* Reserve / Unreserve of one pod on one node.  With anti-affinity tracking on (spec S12) qs_reserve
+ * also records the pod under pod->app on the node, and qs_unreserve removes one pod of that app from
+ * it: the (app, zone) count drops by one and the presence bit clears with the node's last pod of the
+ * app; unreserving an app with nothing recorded on the node returns QS_EINVAL and changes nothing. */
 QS_API qs_status qs_reserve(qs_ctx *ctx, uint32_t node, const qs_pod *pod);
 QS_API qs_status qs_unreserve(qs_ctx *ctx, uint32_t node, const qs_pod *pod);
 
 /* ---- one pod, all nodes (framework-embedded path) ----
  * feasible_n (nullable): 1/0 per node; score_n (nullable): [n][4] {LeastAllocated, Balanced,
  * TaintToleration, NodeAffinity} normalized plugin scores (0 where infeasible); total_n (nullable):
- * QoS-weighted total per node (-1 where infeasible); best: node index of spec S7 or -1. */
+ * QoS-weighted total per node (-1 where infeasible); best: node index of spec S7 or -1.
+ * With anti-affinity tracking on (spec S12) a node the pod's required anti-affinity excludes is
+ * infeasible like any other: 0 in feasible_n, zeros in score_n, -1 in total_n, 0xFFFFFFFF in the
+ * packed words, and outside the normalize maxima. */
 QS_API qs_status qs_score_pod(qs_ctx *ctx, const qs_pod *pod, uint8_t *feasible_n, int32_t *score_n,
                        int32_t *total_n, int32_t *best);
 /* The same call without the per-node copy-out: *packed_n (nullable) points at n context-owned words,

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""What required pod anti-affinity costs on the exact engines: config-5 pods with the
+apps folded to 40 groups and the zones to 4, 100,000 pods on tables of 2,000 and 5,000 nodes.
+
+Arms per table:
+  batched1          QS_MODE_BATCHED with batch_pods = 1: the only route to the sequential semantics with
+                    anti-affinity before qs_set_pod_anti_affinity (one select, merge and claim per pod);
+                    the yardstick, and the one arm a tree without the call can run (--tree)
+  aa_persistent     tracking on, QS_MODE_EXACT, QS_ENGINE_PERSISTENT (tables within its cap; else skipped)
+  aa_scan           tracking on, QS_ENGINE_SCAN
+  plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
+  plain_scan        the cost of the filter and the recording is aa_* against plain_*
+
+Each arm runs in a process of its own, is checked bit for bit on the first 2,000 pods scheduled as a
+stream of their own (tracked arms and batched1 against tests/antiaffinity_ref.py, plain arms against
+oracle.schedule), and prints the median wall of --steps runs of the prepared stream from the same saved
+table (the first run warms up), as us per pod.  --tree DIR runs the arms against another checkout's
+library and binding (the parent commit: batched1 and the plain arms).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARMS = ["batched1", "aa_persistent", "aa_scan", "plain_persistent", "plain_scan"]
+
+
+def paths(tree):
+    # the library and binding of `tree`; the reference and its inputs always from this checkout
+    for p in (os.path.join(ROOT, "tests"), tree, os.path.join(tree, "custom-k8s-scheduler_amd")):
+        sys.path.insert(0, p)
+
+
+def run_arm(n, p, arm, steps, prefix):
+    import numpy as np
+
+    import antiaffinity_ref as A
+    from oracle import oracle as O
+    from qsched import Scheduler, synth_generate
+
+    nodes, pods = synth_generate(5, n, p)
+    nodes, pods = A.fold(nodes, pods, 40, 4)
+    tracked = arm.startswith("aa_")
+    batched = arm == "batched1"
+    engine = "auto" if batched else arm.split("_")[1]
+    cfg = dict(engine=engine, batch_pods=1) if batched else dict(engine=engine)
+    mode = "batched" if batched else "exact"
+    out = dict(nodes=n, pods=p, arm=arm)
+    with Scheduler(cfg) as s:
+        if tracked:
+            s.set_pod_anti_affinity(True)
+        s.load_nodes(nodes)
+        s.save_table()
+        head = s.prepare(pods[:prefix])
+        try:
+            head.run(mode=mode)
+        except Exception as e:  # e.g. PERSISTENT beyond its cap for this class
+            head.free()
+            out.update(skipped=str(e))
+            return out
+        pl, keys = head.results()
+        head.free()
+        if tracked or batched:
+            ref = A.run(nodes, pods[:prefix])
+        else:
+            on = {k: v.copy() for k, v in nodes.items()}
+            ref = O.schedule(on, A.pods_dict(pods[:prefix]))
+        out["prefix_ok"] = bool(np.array_equal(pl, ref[0]) and np.array_equal(keys, ref[1]))
+        s.restore_table()
+        st = s.prepare(pods)
+        walls, stats = [], None
+        for i in range(steps + 1):
+            stats = st.run(mode=mode)
+            if i:
+                walls.append(stats["wall_s"])
+            s.restore_table()
+        st.free()
+    wall = statistics.median(walls)
+    out.update(ms_per_step=round(wall * 1e3, 3), ms_all=[round(w * 1e3, 3) for w in walls],
+               us_per_pod=round(wall * 1e6 / p, 3), engine_used=stats["engine_used"], launches=int(stats["batches"]))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--nodes", default="2000,5000")
+    ap.add_argument("--pods", type=int, default=100000)
+    ap.add_argument("--arms", default=",".join(ARMS))
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--prefix", type=int, default=2000)
+    ap.add_argument("--tree", default=ROOT, help="checkout whose library and binding run the arms")
+    ap.add_argument("--one", nargs=2, metavar=("NODES", "ARM"), help="run one arm in this process")
+    a = ap.parse_args()
+    if a.one:
+        paths(os.path.abspath(a.tree))
+        print(json.dumps(run_arm(int(a.one[0]), a.pods, a.one[1], a.steps, a.prefix)), flush=True)
+        return 0
+    rows, bad = [], 0
+    for n in (int(x) for x in a.nodes.split(",")):
+        for arm in a.arms.split(","):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(n), arm, "--pods", str(a.pods),
+                                "--steps", str(a.steps), "--prefix", str(a.prefix), "--tree", a.tree],
+                               capture_output=True, text=True, timeout=420)
+            if r.returncode != 0:
+                # a failed arm may have left the device in a bad state: nothing more is started
+                sys.stderr.write(r.stdout + r.stderr)
+                print(f"arm {n}/{arm} exited with {r.returncode}; stopping", flush=True)
+                return 1
+            row = json.loads(r.stdout.strip().splitlines()[-1])
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            bad += not row.get("prefix_ok", True)
+    for n in sorted({r["nodes"] for r in rows}):
+        base = next((r for r in rows if r["nodes"] == n and r["arm"] == "batched1" and "us_per_pod" in r), None)
+        for r in rows:
+            if r["nodes"] != n:
+                continue
+            if "skipped" in r:
+                print(f"n {n:5d} {r['arm']:17s} skipped: {r['skipped'][:90]}")
+                continue
+            rel = f"x{r['us_per_pod'] / base['us_per_pod']:.3f} of batched1" if base else ""
+            print(f"n {n:5d} {r['arm']:17s} {r['ms_per_step']:10.3f} ms  {r['us_per_pod']:8.3f} us/pod  {rel}  "
+                  f"engine {r['engine_used']}  prefix {'ok' if r['prefix_ok'] else 'DIFFERS'}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
