@@ -103,6 +103,14 @@ struct Mirror {
         if (left <= 0) aa_node.erase(it);
         return left;
     }
+    // The topology domains of spec S13: bit z set iff zone z holds a node of the table, whatever its
+    // state.  Recomputed from the zone column wherever it is needed (a load, a re-layout, an upsert that
+    // changes a zone or appends): nothing is kept, so save / restore and rebuilds need no upkeep.
+    uint64_t domains() const {
+        uint64_t d = 0;
+        for (uint32_t i = 0; i < n; i++) d |= 1ull << ((uint32_t)zone[i] & (qs::kMaxZones - 1));
+        return d;
+    }
     bool aa_holds(uint32_t node) const { return node < aa_pods.size() && aa_pods[node] > 0; }
     int32_t aa_count(uint32_t app, uint32_t node) const {
         auto it = aa_node.find(((uint64_t)app << 32) | node);
@@ -135,6 +143,11 @@ struct qs_stream {
     int mode_ran = -1;        // qs_mode of the last run
     uint64_t epoch_after = 0;  // the context's table epoch right after the last run (FitError replay)
     bool aa_ran = false;       // the last run filtered by pod anti-affinity (spec S12: no FitError replay)
+    // Zone topology spread (spec S13): the distinct apps of the stream's QS_AA_SPREAD pods as the row
+    // k_persistent reads (slot j -> app, -1 = unused; the first kSpreadApps of them), and their number
+    // (above kSpreadApps the stream does not run PERSISTENT with tracking on)
+    int32_t spread_row[qs::kMaxZones];
+    uint32_t spread_apps = 0;
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
     // Uniform windows: run0[k] = first stream position of the run of byte-identical

@@ -60,6 +60,11 @@ struct DevSoa {
 // presence bit (word-major: word w of node i at apps[w * cap + i], so a wave over consecutive
 // nodes reads consecutive words), per (app, zone) a pod count.  apps == nullptr: not kept.
 constexpr uint32_t kMaxApps = 1024, kMaxZones = 64, kAppWords = kMaxApps / 32;
+// Zone topology spread (spec S13): two more rows of kMaxZones words behind zcount[kMaxApps], the domain
+// flags (row kMaxApps) and the spread apps of a PERSISTENT stream (row kMaxApps + 1, kSpreadApps
+// entries, -1 = unused; the LDS slots of k_persistent).
+constexpr uint32_t kSpreadRows = 2, kSpreadApps = 64;
+static_assert(kSpreadApps <= kMaxZones, "the spread apps fill one row");
 struct DevTable {
     DRow *rows;       // compact layout (nullptr in the wide layout)
     DRowW *wrows;     // wide layout (nullptr in the compact layout)
@@ -68,7 +73,7 @@ struct DevTable {
     DevSoa soa;
     int32_t *zone;
     uint32_t *apps;
-    int32_t *zcount;  // [kMaxApps][kMaxZones]
+    int32_t *zcount;  // [kMaxApps][kMaxZones] (+ kSpreadRows rows, see below)
     uint32_t cap;     // row capacity (stride of the app words)
 };
 

@@ -288,7 +288,9 @@ size_t carve(DevTable &t, uint32_t cap, bool wide, char *base) {
     t.cap = cap;
     if (cap <= kAaMaxNodes) {
         t.apps = (uint32_t *)take((size_t)kAppWords * cap * 4);
-        t.zcount = (int32_t *)take((size_t)kMaxApps * kMaxZones * 4);
+        // ... and behind the counts, in the same allocation (so qs_table_save / restore carry them), the
+        // two rows of spec S13: the domain flags and the spread apps of the PERSISTENT stream in flight
+        t.zcount = (int32_t *)take((size_t)(kMaxApps + kSpreadRows) * kMaxZones * 4);
     } else {
         t.apps = nullptr;
         t.zcount = nullptr;
@@ -316,6 +318,21 @@ DRowW to_drow_wide(const HostRow &r) {
     d.yc = r.yc; d.mp = r.mp; d.pad = 0;
     d.ae0 = r.ae0; d.re0 = r.re0; d.ae1 = r.ae1; d.re1 = r.re1;
     return d;
+}
+
+// The two rows of spec S13 behind the (app, zone) counts: the domain flags from the mirror's zone
+// column, and an empty spread-app list (a PERSISTENT stream writes its own before it launches).
+void write_domains(qs_ctx *c) {
+    if (!c->dt.zcount) return;
+    int32_t rows[kSpreadRows * kMaxZones];
+    const uint64_t dom = c->m.domains();
+    for (uint32_t z = 0; z < kMaxZones; z++) {
+        rows[z] = (int32_t)((dom >> z) & 1u);
+        rows[kMaxZones + z] = -1;
+    }
+    HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)kMaxApps * kMaxZones, rows, sizeof rows, hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (rows lives on this stack)
 }
 
 // Upload the whole mirror to the device in the context's layout (c->wide, c->shift).
@@ -370,6 +387,7 @@ void upload_table(qs_ctx *c) {
             HIPCHK(hipMemsetAsync(c->dt.apps, 0, (size_t)kAppWords * c->cap * 4, c->stream));
             HIPCHK(hipMemsetAsync(c->dt.zcount, 0, (size_t)kMaxApps * kMaxZones * 4, c->stream));
         }
+        write_domains(c);
     }
     if (soa) {
         c->soa.ensure(cols.size() * 4);
@@ -459,17 +477,29 @@ void check_pod(const qs_pod &p, uint32_t j) {
     for (int t = 0; t < p.n_pref_terms; t++)
         if (p.pref_weight[t] < 0 || p.pref_weight[t] > 100) bad("preferred term weight must be 0..100");
     if (p.app < 0 || p.app >= QS_MAX_APPS) bad("app outside [0, QS_MAX_APPS)");
-    if (p.anti_affinity < QS_AA_NONE || p.anti_affinity > QS_AA_ZONE) bad("anti_affinity must be 0..2");
+    // one kind per pod in the low byte; QS_AA_SPREAD_ZONE carries max_skew in bits 8-12 (spec S13)
+    const int32_t kind = QS_AA_KIND(p.anti_affinity);
+    if (p.anti_affinity < 0 || kind > QS_AA_SPREAD_ZONE) bad("anti_affinity kind must be 0..3");
+    if (kind == QS_AA_SPREAD_ZONE) {
+        const int32_t skew = p.anti_affinity >> 8;
+        if (skew < 1 || skew > QS_MAX_SPREAD_SKEW) bad("anti_affinity: max_skew of QS_AA_SPREAD must be 1..31");
+    } else if (p.anti_affinity != kind) {
+        bad("anti_affinity: bits above the kind must be zero (only QS_AA_SPREAD carries max_skew)");
+    }
 }
+bool pod_spreads(const qs_pod &p) { return QS_AA_KIND(p.anti_affinity) == QS_AA_SPREAD_ZONE; }
 
 // NodeAffinity disabled (config.enable_affinity = 0): the pod's required / preferred term counts are
 // recorded as 0, so the normalizing kernels (which evaluate both plugins) neither filter nor score
 // by affinity.  Bits 2-3: the strategy of the pod's QoS class (qs_scoring_strategy_type), which only
-// the kFeatStrat scorer reads (check_pod has bounded qos to 0..2).
+// the kFeatStrat scorer reads (check_pod has bounded qos to 0..2).  Bits 12-13: the anti-affinity kind;
+// bits 26-30: max_skew of a QS_AA_SPREAD pod (0 for every other kind; spec S13, read by the kFeatAA
+// kernels only).  Bit 31 stays the batched claim's.
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
     return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
-           (aff * (uint32_t)p.n_pref_terms << 8) | ((uint32_t)p.anti_affinity << 12) | ((uint32_t)p.app << 16);
+           (aff * (uint32_t)p.n_pref_terms << 8) | ((uint32_t)QS_AA_KIND(p.anti_affinity) << 12) |
+           ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
 }
 
 // Device pod record in the context's layout: DPod (compact, memory in 2^shift units) or DPodW
@@ -722,7 +752,7 @@ struct KernelTimer {
 uint32_t la_window(const qs_ctx *c);
 bool la_overlap(const qs_ctx *c);
 
-int pick_engine(const qs_ctx *c, uint32_t n) {
+int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false) {
     int e = c->cfg.engine;
     const uint32_t feat = c->dc.feat;
     if (feat & kFeatAA) {
@@ -730,7 +760,14 @@ int pick_engine(const qs_ctx *c, uint32_t n) {
         if (e == QS_ENGINE_LOOKAHEAD || e == QS_ENGINE_ALLREDUCE)
             fail(QS_EINVAL, "pod anti-affinity tracking runs the PERSISTENT and SCAN engines only: the lookahead "
                             "lists and the per-pod all-reduce do not carry the anti-affinity filter");
-        if (e == QS_ENGINE_AUTO) e = n <= persistent_max_nodes(feat) ? QS_ENGINE_PERSISTENT : QS_ENGINE_SCAN;
+        // zone topology spread (spec S13): a stream whose SPREAD pods belong to more apps than the
+        // persistent workgroup keeps counts for (kSpreadApps) runs SCAN, like a table
+        // above the node cap
+        if (spread_over && e == QS_ENGINE_PERSISTENT)
+            fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD pods of at most " + std::to_string(kSpreadApps) +
+                                " distinct apps per stream");
+        if (e == QS_ENGINE_AUTO)
+            e = n <= persistent_max_nodes(feat) && !spread_over ? QS_ENGINE_PERSISTENT : QS_ENGINE_SCAN;
     }
     if (e == QS_ENGINE_AUTO) {
         if (n > 0 && la_geometry(n, la_window(c), shard_plan(c).W, 2 * la_window(c)).G > 0)
@@ -1181,6 +1218,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
             fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
                             "cannot change while tracking is on");
         const bool was_zero = idx < m.n && zero_alloc_row(m, idx);
+        const bool zone_moves = idx < m.n && r->zone != m.zone[idx];  // (an append re-uploads the table)
         if (idx == m.n) {  // append one node
             // (the recorded anti-affinity state is moved aside, not copied with the columns)
             auto aa_node = std::move(m.aa_node);
@@ -1212,7 +1250,12 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         const int old_shift = c->shift;
         const bool old_wide = c->wide;
         ensure_layout(c, nullptr, 0, want);
-        if (was_valid && c->dev_valid && c->shift == old_shift && c->wide == old_wide) push_row(c, idx);
+        if (was_valid && c->dev_valid && c->shift == old_shift && c->wide == old_wide) {
+            push_row(c, idx);
+            // a zone may have gained its first node or lost its last: the domains of spec S13 (every
+            // other path re-uploads the table, upload_table writes them)
+            if (zone_moves) write_domains(c);
+        }
     });
 }
 
@@ -1568,6 +1611,18 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         if (has_ext) s->feat |= kFeatExt;
         s->feat |= res_feat(c->cfg, has_ext) | strat_feat(c, pods, p);
         s->order = qos_order(pods, p, c->cfg.qos_sort != 0);
+        {  // the distinct apps of the SPREAD pods (spec S13), in arrival order.  k_persistent relies on
+           // this: every SPREAD pod's app is in the row (pick_engine keeps a stream with more than
+           // kSpreadApps of them off PERSISTENT); a pod whose app had no slot would be allowed no zone
+            std::vector<uint8_t> seen(kMaxApps, 0);
+            std::fill(std::begin(s->spread_row), std::end(s->spread_row), -1);
+            for (uint32_t j = 0; j < p; j++) {
+                if (!pod_spreads(pods[j]) || seen[(uint32_t)pods[j].app]) continue;
+                seen[(uint32_t)pods[j].app] = 1;
+                if (s->spread_apps < kSpreadApps) s->spread_row[s->spread_apps] = pods[j].app;
+                ++s->spread_apps;
+            }
+        }
         const size_t rb = pod_record_bytes(c->wide);
         std::vector<uint8_t> dp(rb * std::max<uint32_t>(p, 1));
         const bool needx = feat_of(c->cfg) & (kFeatTaint | kFeatAffinity);
@@ -1607,6 +1662,9 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         if (!s) fail(QS_EINVAL, "null stream");
         if (mode != QS_MODE_EXACT && mode != QS_MODE_BATCHED) fail(QS_EINVAL, "unknown qs_mode");
         if (s->shift != c->shift || s->wide != c->wide) fail(QS_ESTATE, "node table re-laid out after prepare");
+        if (mode == QS_MODE_BATCHED && s->spread_apps != 0)
+            fail(QS_EINVAL, "QS_MODE_BATCHED does not know zone topology spread (QS_AA_SPREAD pods, spec S13): "
+                            "run the stream in QS_MODE_EXACT on a context that tracks pod anti-affinity");
         HIPCHK(hipSetDevice(c->device));
         // from here on the device table (and d_node) may change even if this run fails part way
         // (e.g. a resident timeout): invalidate the stream's results and every other stream's FitError
@@ -1624,7 +1682,12 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         const bool aa_exact = c->aa_track && mode == QS_MODE_EXACT;
         if (c->aa_track) aa_check_table(c);
         if (aa_exact) c->dc.feat = aa_feat(s->feat);
-        const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n);
+        // zone topology spread (spec S13): k_persistent keeps the counts of at most kSpreadApps apps
+        const bool spread_over = aa_exact && s->spread_apps > kSpreadApps;
+        const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n, spread_over);
+        if (aa_exact && eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
+            HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 1) * kMaxZones, s->spread_row,
+                                  sizeof s->spread_row, hipMemcpyHostToDevice, c->stream));
         int32_t *on = s->d_node.as<int32_t>();
         uint64_t *ok = s->d_key.as<uint64_t>();
         uint64_t *st = c->cfg.record_timestamps ? s->d_stamp.as<uint64_t>() : nullptr;

@@ -54,6 +54,52 @@ __device__ __forceinline__ uint8_t *aa_lds_zone() {
     return zl;
 }
 
+// Zone topology spread (kind 3 of the kFeatAA family, spec S13).  Two 256-byte rows behind
+// zcount[kMaxApps] in the same allocation carry what the host provides: the domain flags (entry z != 0
+// iff zone z holds a node of the table) and, for k_persistent, the apps of the stream's SPREAD pods
+// (entry j = app id of LDS slot j, -1 = unused).  max_skew travels in pod-flag bits 26-30.
+__device__ __forceinline__ uint32_t pod_skew(uint32_t flags) { return (flags >> 26) & 31u; }
+__device__ __forceinline__ const int32_t *aa_domain_row(const DevTable &t) { return t.zcount + kMaxApps * kMaxZones; }
+__device__ __forceinline__ const int32_t *aa_spread_row(const DevTable &t) {
+    return t.zcount + (kMaxApps + 1) * kMaxZones;
+}
+// The allowed-zones word of one SPREAD pod; every lane of the wave must be active.  Lane z holds the
+// app's recorded pods c of zone z (>= 0) and whether z is a domain.  The minimum over the domains is
+// a DPP wave max of INT_MAX - c (absent zones contribute 0, i.e. INT_MAX to the minimum); bit z of
+// the result is set iff z is a domain and c + 1 - min <= skew.  Wave-uniform.
+__device__ __forceinline__ uint64_t spread_allowed(int32_t c, bool present, uint32_t skew) {
+    const uint32_t inv = present ? 0x7FFFFFFFu - (uint32_t)c : 0u;
+    const int32_t m = (int32_t)(0x7FFFFFFFu - wave_max_u32(inv));
+    return __ballot(present && c + 1 - m <= (int32_t)skew);
+}
+// The same word from global memory, once per launch and wave (SCAN and the score path: the counts of
+// the pod's turn are a kernel boundary behind); ~0 for every other kind.  Call it before any
+// divergent code: the flags are wave-uniform, so the branch is too.
+__device__ __forceinline__ uint64_t spread_word(const DevTable &t, uint32_t flags) {
+    if (pod_aa(flags) != 3u) return ~0ull;
+    const uint32_t z = threadIdx.x & 63u;
+    const int32_t c = t.zcount[pod_app(flags) * kMaxZones + z];
+    return spread_allowed(c, aa_domain_row(t)[z] != 0, pod_skew(flags));
+}
+__device__ __forceinline__ bool spread_ok(const DevTable &t, uint32_t flags, uint64_t zw, uint32_t i) {
+    return pod_aa(flags) != 3u || ((zw >> (uint32_t)t.zone[i]) & 1ull) != 0;
+}
+// k_persistent keeps the counts of the stream's spread apps in LDS (global zcount cannot be read back
+// inside the launch: thread 0's atomic add is not waited for), twice: the pod at stream position s
+// reads copy s & 1, and thread 0 brings that copy up to date after the pod's barrier, when no thread
+// reads it any more (see the kernel).  Behind the two copies: the domain flags, and one word in which
+// thread 0 remembers the cell it bumped for the previous pod (-1: none).  Plus the app -> slot map
+// (0xFF: none).
+constexpr uint32_t kSpcDomains = 2 * kSpreadApps * kMaxZones, kSpcLast = kSpcDomains + kMaxZones;
+__device__ __forceinline__ int32_t *aa_lds_spread() {
+    __shared__ int32_t sc[kSpcLast + 1];
+    return sc;
+}
+__device__ __forceinline__ uint8_t *aa_lds_slot() {
+    __shared__ uint8_t slot[kMaxApps];
+    return slot;
+}
+
 template <int NPT, int BS, uint32_t F>
 __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__restrict__ pods,
                                                    const DPodX *__restrict__ podx, uint32_t P,
@@ -80,6 +126,11 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
     [[maybe_unused]] uint8_t *zl = nullptr;
     [[maybe_unused]] uint32_t prev_app = 0;
     [[maybe_unused]] uint64_t prev_bit = 0;
+    // ... SPREAD: the LDS counts (and, behind them, the domain flags) and the app -> slot map: static
+    // LDS addresses, nothing more is carried over the pod loop
+    [[maybe_unused]] int32_t *spc = nullptr;
+    [[maybe_unused]] uint8_t *slot = nullptr;
+    [[maybe_unused]] bool spread = false;  // the stream has spread apps (uniform over the workgroup)
     if constexpr ((F & kFeatAA) != 0) {
         zmask = aa_lds_zmask();
         zl = aa_lds_zone<NPT * BS>();
@@ -101,6 +152,28 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
             }
             zmask[a] = m;
         }
+        // SPREAD (spec S13): the slot map (0xFF = no slot: every app of a stream without SPREAD pods),
+        // the LDS counts of the stream's spread apps (slot j of the host's list) and the domain flags
+        spc = aa_lds_spread();
+        slot = aa_lds_slot();
+        for (uint32_t a = tid; a < kMaxApps; a += BS) slot[a] = 0xFFu;
+        __syncthreads();
+        const int32_t sa = aa_spread_row(t)[lane];
+        const bool sav = sa >= 0 && sa < (int32_t)kMaxApps;
+        if (w == 0) {
+            if (sav) slot[sa] = (uint8_t)lane;
+            spc[kSpcDomains + lane] = aa_domain_row(t)[lane];
+            if (lane == 0) spc[kSpcLast] = -1;
+        }
+        spread = __ballot(sav) != 0;  // (every wave reads the same list)
+        if (spread) {
+            for (int j = w; j < (int)kSpreadApps; j += NW) {
+                const int32_t a = __shfl(sa, j);
+                const int32_t v = (a >= 0 && a < (int32_t)kMaxApps) ? t.zcount[(uint32_t)a * kMaxZones + lane] : 0;
+                spc[j * kMaxZones + lane] = v;
+                spc[(kSpreadApps + j) * kMaxZones + lane] = v;
+            }
+        }
         __syncthreads();
     }
     PodT<F> pn = pods[0];
@@ -118,9 +191,26 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
         [[maybe_unused]] uint32_t aam = ~0u;
         if constexpr ((F & kFeatAA) != 0) {
             const uint32_t kind = pod_aa(p.flags), app = pod_app(p.flags);
-            if (kind == 2u) {
-                uint64_t zw = __hip_atomic_load(&zmask[app], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                zw |= app == prev_app ? prev_bit : 0ull;
+            if (kind >= 2u) {
+                uint64_t zw;
+                if (kind == 2u) {
+                    zw = __hip_atomic_load(&zmask[app], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    zw |= app == prev_app ? prev_bit : 0ull;
+                } else {
+                    // SPREAD (spec S13): the zones the pod may NOT take, in the ZONE word's form.  All
+                    // 64 lanes are active here (top of the pod's scope).  Lane z reads the count of
+                    // zone z from copy s & 1, which holds every pod before the previous one (thread 0
+                    // wrote it two barriers ago at the latest) and is not written during this pod's
+                    // reads; the previous pod's own +1 comes from the registers every thread carries.
+                    // The host lists every SPREAD pod's app (qs_stream_prepare); an app without a slot
+                    // (0xFF) would have no counts here, so such a pod is allowed nothing rather than
+                    // filtered against another app's counts.
+                    const uint32_t sl = slot[app];
+                    int32_t cz = spc[((s & 1u) * kSpreadApps + (sl & (kSpreadApps - 1u))) * kMaxZones + lane];
+                    cz += (app == prev_app && ((prev_bit >> lane) & 1ull)) ? 1 : 0;
+                    const uint64_t ok = spread_allowed(cz, spc[kSpcDomains + lane] != 0, pod_skew(p.flags));
+                    zw = sl < kSpreadApps ? ~ok : ~0ull;
+                }
 #pragma unroll
                 for (int k = 0; k < NPT; ++k) aam &= ~((uint32_t)((zw >> zn[k]) & 1ull) << k);
             } else if (kind == 1u) {
@@ -189,6 +279,21 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
             // of this stream and in global memory for the launches after it (one workgroup runs
             // the stream, so nothing here is read by another CU before the kernel ends)
             const uint32_t app = pod_app(p.flags);
+            // SPREAD counts (spec S13), only in a stream that has spread apps: every thread is past
+            // this pod's barrier, so nobody reads copy s & 1 before the barrier after the next; thread 0
+            // adds this pod and the previous one (which went to the other copy only) to it, each if it
+            // was placed and its app has a slot.  The previous pod's cell is a word only thread 0 reads
+            // and writes (program order), so nothing more is carried in registers and prev_bit has
+            // no new reader.
+            if (spread && tid == 0) {
+                int32_t *b = spc + (s & 1u) * (kSpreadApps * kMaxZones);
+                const uint32_t sl = ks != 0 ? (uint32_t)slot[app] : 0xFFu;
+                const int32_t cell = sl < kSpreadApps ? (int32_t)(sl * kMaxZones + zl[win]) : -1;
+                const int32_t last = spc[kSpcLast];
+                if (cell >= 0) b[cell] += 1;
+                if (last >= 0) b[last] += 1;
+                spc[kSpcLast] = cell;
+            }
             prev_app = app;
             prev_bit = 0;
             if (ks != 0) {
@@ -257,12 +362,14 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
     const PodT<F> p = pods[s];
     const DPodX px = podx[s];
     uint32_t lt = 0, la = 0;
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         if (f) {
             const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
             lt = a > lt ? a : lt;
@@ -290,12 +397,14 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
     if (F & kFeatNorm) { px = podx[s]; mt = sc->mt; ma = sc->ma; }
     const double ymt = rcp_exact(mt), yma = rcp_exact(ma);
     uint64_t best = 0;
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         uint32_t sco[4];
         // (kFeatAA classes: the scores always go to the local array, which then stays in registers;
         // the pointer select of the older classes keeps their heavier scorers' array in scratch)
@@ -334,6 +443,8 @@ __global__ __launch_bounds__(256) void k_scan_soa(DevTable t, const PodT<F> *__r
     const DPodX px{};
     const uint32_t nq = (t.n + 3) / 4;  // columns are zero-padded to a multiple of 64 nodes
     uint64_t best = 0;
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     // two quads per lane in flight: both iterations' loads are issued before either is scored
     const uint32_t stride = gridDim.x * 256;
     for (uint32_t q0 = blockIdx.x * 256 + threadIdx.x; q0 < nq; q0 += 2 * stride) {
@@ -366,7 +477,8 @@ __global__ __launch_bounds__(256) void k_scan_soa(DevTable t, const PodT<F> *__r
             const uint32_t idx = 4 * q + e;
             bool f = feasible<F>(r, x, p, px);  // padding rows: max_pods 0 -> infeasible
             // (the zone column is read for ZONE pods only; padding rows have no zone)
-            if constexpr ((F & kFeatAA) != 0) f = f && idx < t.n && aa_ok(t, p.flags, idx);
+            if constexpr ((F & kFeatAA) != 0)
+                f = f && idx < t.n && aa_ok(t, p.flags, idx) && spread_ok(t, p.flags, zw, idx);
             uint32_t sco[4];
             const uint32_t tot = node_total<F>(r, x, p, px, c, 0, 0.0, 0, 0.0,
                                                ((F & kFeatAA) != 0 || score_out) ? sco : nullptr);
@@ -504,6 +616,8 @@ __global__ __launch_bounds__(1024) void k_score_pod1(DevTable t, PodT<F> p, DPod
     RowT<F> pr;
     RowX prx;
     host_row_regs<F>(prow, pr, prx);
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     if (tid == 0 && pidx < n) set_row(t, pidx, prow);
     auto row_at = [&](uint32_t i, RowT<F> &r, RowX &x) {
         r = load_row<F>(t, i);
@@ -517,7 +631,7 @@ __global__ __launch_bounds__(1024) void k_score_pod1(DevTable t, PodT<F> p, DPod
             RowX x;
             row_at(i, r, x);
             bool f = feasible<F>(r, x, p, px);
-            if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+            if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
             if (f) {
                 const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
                 mt = a > mt ? a : mt;
@@ -541,7 +655,7 @@ __global__ __launch_bounds__(1024) void k_score_pod1(DevTable t, PodT<F> p, DPod
         RowX x;
         row_at(i, r, x);
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         uint32_t sco[4];
         const uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma, sco);
         const uint64_t key = f ? pack_key(tot + 1, i) : 0ull;
@@ -576,6 +690,8 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     static_assert((F & kFeatNorm) != 0, "maxima of the normalizing plugins only");
     const uint32_t n = t.n, i = blockIdx.x * kScorePodGT + threadIdx.x;
     uint32_t mt = 0, ma = 0;
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     if (i < n) {
         RowT<F> r;
         RowX x;
@@ -586,7 +702,7 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
             x = load_rowx<F>(t, i);
         }
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         if (f) {
             mt = taint_raw(x, px);
             ma = affinity_raw(x, p, px);
@@ -607,6 +723,8 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
     __shared__ uint64_t redk[NW];
     const uint32_t n = t.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t i = blockIdx.x * kScorePodGT + tid;
+    [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     if (blockIdx.x == 0 && tid == 0 && pidx < n) set_row(t, pidx, prow);
     uint32_t mt = 0, ma = 0;
     if constexpr ((F & kFeatNorm) != 0) {  // k_score_podg_max's maxima (the previous launch)
@@ -624,7 +742,7 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
             x = load_rowx<F>(t, i);
         }
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i);
+        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         uint32_t sco[4];
         const uint32_t tot = node_total<F>(r, x, p, px, c, mt, rcp_exact(mt), ma, rcp_exact(ma), sco);
         best = f ? pack_key(tot + 1, i) : 0ull;

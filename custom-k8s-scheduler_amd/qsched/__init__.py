@@ -25,9 +25,32 @@ from ._abi import (ENGINES, ENGINE_NAMES, EXPORTED, LIB_PATH, POD_DTYPE, QS_ABI_
 
 __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_struct", "fit_error_message",
            "synth_generate", "shape_table", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
-           "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH"]
+           "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH",
+           "aa_spread", "aa_kind", "aa_max_skew", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
+           "QS_MAX_SPREAD_SKEW"]
+
+from ._abi import (QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
+                   QS_MAX_SPREAD_SKEW)
 
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
+
+
+def aa_spread(max_skew: int) -> int:
+    """QS_AA_SPREAD(max_skew): the ``anti_affinity`` value of a pod under zone topology spread
+    (``topologySpreadConstraints``, ``whenUnsatisfiable: DoNotSchedule``, spec S13), max_skew 1..31."""
+    if not 1 <= int(max_skew) <= QS_MAX_SPREAD_SKEW:
+        raise ValueError("max_skew must be 1..31")
+    return QS_AA_SPREAD_ZONE | (int(max_skew) << 8)
+
+
+def aa_kind(anti_affinity):
+    """QS_AA_KIND: the kind in the low byte (scalar or array)."""
+    return anti_affinity & 0xFF
+
+
+def aa_max_skew(anti_affinity):
+    """QS_AA_MAX_SKEW: bits 8-12 (0 for every kind but QS_AA_SPREAD_ZONE)."""
+    return (anti_affinity >> 8) & 0x1F
 NODE_I64 = ["alloc_cpu", "alloc_mem", "max_pods", "req_cpu", "req_mem", "nz_cpu", "nz_mem", "pods"]
 
 

@@ -72,8 +72,21 @@ typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
 /* Required pod anti-affinity to the pod's own app group (the subset of UP plugins/interpodaffinity
  * that config 5 uses): none, per node (topologyKey hostname), per zone.  QS_MODE_BATCHED always
  * honours it (spec S11); exact streams, qs_score_pod and qs_reserve / qs_unreserve honour it on a
- * context that tracks it (qs_set_pod_anti_affinity, spec S12) and ignore it otherwise. */
-typedef enum qs_anti_affinity { QS_AA_NONE = 0, QS_AA_HOSTNAME = 1, QS_AA_ZONE = 2 } qs_anti_affinity;
+ * context that tracks it (qs_set_pod_anti_affinity, spec S12) and ignore it otherwise.
+ * QS_AA_SPREAD_ZONE (spec S13) is the zone topologySpreadConstraint with whenUnsatisfiable:
+ * DoNotSchedule over the pod's own app (UP plugins/podtopologyspread Filter; nodeAffinityPolicy and
+ * nodeTaintsPolicy Ignore, minDomains unset): a node is infeasible when taking it would leave its zone
+ * more than max_skew pods of the app above the emptiest zone that holds a node of the table.  The kind
+ * sits in the low byte of qs_pod.anti_affinity and max_skew (1..31) in bits 8-12: QS_AA_SPREAD(max_skew).
+ * Upper bits must be zero for the other kinds; a pod has one kind.  Honoured like the other kinds on a
+ * context that tracks; QS_MODE_BATCHED refuses a stream that holds such a pod (QS_EINVAL). */
+typedef enum qs_anti_affinity {
+    QS_AA_NONE = 0, QS_AA_HOSTNAME = 1, QS_AA_ZONE = 2, QS_AA_SPREAD_ZONE = 3
+} qs_anti_affinity;
+#define QS_AA_SPREAD(max_skew) ((int32_t)(QS_AA_SPREAD_ZONE | ((max_skew) << 8)))
+#define QS_AA_KIND(x) ((int32_t)((x) & 0xFF))
+#define QS_AA_MAX_SKEW(x) ((int32_t)(((x) >> 8) & 0x1F))
+#define QS_MAX_SPREAD_SKEW 31
 
 /* Scoring resources (spec/semantics.md S5 "Scoring resources"): cpu, memory, or one of the table's
  * two extended-resource columns (the caller interns e.g. "amd.com/gpu" as QS_RES_EXT0). */
@@ -198,7 +211,9 @@ typedef struct qs_pod {
     int32_t app;           /* anti-affinity group (< QS_MAX_APPS); with tracking on (spec S12) every
                               placed pod is recorded under it, whatever its anti_affinity */
     int32_t anti_affinity; /* qs_anti_affinity: required anti-affinity to the pod's own app (batched
-                              mode; exact mode and the score path with tracking on, else ignored) */
+                              mode; exact mode and the score path with tracking on, else ignored), or
+                              QS_AA_SPREAD(max_skew): zone topology spread (spec S13; exact mode and the
+                              score path with tracking on, else ignored; refused by batched mode) */
 } qs_pod;
 
 /* One container of a pod spec for qs_pod_from_containers (spec S2/S3). has_* = 0 means missing. */
@@ -294,8 +309,12 @@ QS_API qs_status qs_get_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, qs_scorin
  * marks the device state with tracking off (S11, as before), so pods it places then filter later pods
  * until the table is re-laid out or rebuilt, but qs_unreserve does not know them (QS_EINVAL) and a zone
  * change of their node is not refused.  Switch tracking on before the first stream whose pods should
- * count.  Exact streams then run QS_ENGINE_PERSISTENT
- * (tables that fit it) or QS_ENGINE_SCAN; an explicit QS_ENGINE_LOOKAHEAD / QS_ENGINE_ALLREDUCE makes
+ * count.  QS_AA_SPREAD(max_skew) pods (spec S13) filter against the same (app, zone) counts: every
+ * recorded pod of the app counts, whatever its kind, and the minimum runs over the zones that hold a node
+ * of the table (a qs_node_upsert that opens a new zone lowers it to 0).  Exact streams then run
+ * QS_ENGINE_PERSISTENT (tables that fit it, and streams whose SPREAD pods belong to at most 64 distinct
+ * apps; beyond that AUTO runs SCAN and an explicit PERSISTENT returns QS_EINVAL)
+ * or QS_ENGINE_SCAN; an explicit QS_ENGINE_LOOKAHEAD / QS_ENGINE_ALLREDUCE makes
  * qs_stream_run return QS_EINVAL, as do qs_stream_fit_errors / qs_stream_fit_taints of a tracked run and
  * a qs_node_upsert that moves a node holding recorded pods to another zone.  QS_ESTATE while the context
  * holds prepared streams; QS_EINVAL (switching on) on a sharded context (qs_open_shard, virtual_shards
@@ -325,8 +344,8 @@ QS_API qs_status qs_unreserve(qs_ctx *ctx, uint32_t node, const qs_pod *pod);
  * feasible_n (nullable): 1/0 per node; score_n (nullable): [n][4] {LeastAllocated, Balanced,
  * TaintToleration, NodeAffinity} normalized plugin scores (0 where infeasible); total_n (nullable):
  * QoS-weighted total per node (-1 where infeasible); best: node index of spec S7 or -1.
- * With anti-affinity tracking on (spec S12) a node the pod's required anti-affinity excludes is
- * infeasible like any other: 0 in feasible_n, zeros in score_n, -1 in total_n, 0xFFFFFFFF in the
+ * With anti-affinity tracking on (spec S12, S13) a node the pod's required anti-affinity or its zone
+ * topology spread (QS_AA_SPREAD) excludes is infeasible like any other: 0 in feasible_n, zeros in score_n, -1 in total_n, 0xFFFFFFFF in the
  * packed words, and outside the normalize maxima. */
 QS_API qs_status qs_score_pod(qs_ctx *ctx, const qs_pod *pod, uint8_t *feasible_n, int32_t *score_n,
                        int32_t *total_n, int32_t *best);

@@ -8,6 +8,8 @@ Arms per table:
                     the yardstick, and the one arm a tree without the call can run (--tree)
   aa_persistent     tracking on, QS_MODE_EXACT, QS_ENGINE_PERSISTENT (tables within its cap; else skipped)
   aa_scan           tracking on, QS_ENGINE_SCAN
+  spread_persistent the aa_* arms with the ZONE apps' pods turned into SPREAD(1) (zone topology spread, spec S13,
+  spread_scan       DESIGN.md §3.5), checked against tests/spread_ref.py; read beside aa_* of the same run
   plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
   plain_scan        the cost of the filter and the recording is aa_* against plain_*
 
@@ -25,7 +27,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARMS = ["batched1", "aa_persistent", "aa_scan", "plain_persistent", "plain_scan"]
+ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "plain_persistent", "plain_scan"]
 
 
 def paths(tree):
@@ -43,7 +45,13 @@ def run_arm(n, p, arm, steps, prefix):
 
     nodes, pods = synth_generate(5, n, p)
     nodes, pods = A.fold(nodes, pods, 40, 4)
-    tracked = arm.startswith("aa_")
+    spread = arm.startswith("spread_")
+    tracked = arm.startswith("aa_") or spread
+    if spread:
+        import spread_ref as S
+
+        pods = pods.copy()
+        pods["anti_affinity"][pods["anti_affinity"] == A.ZONE] = S.spread(1)
     batched = arm == "batched1"
     engine = "auto" if batched else arm.split("_")[1]
     cfg = dict(engine=engine, batch_pods=1) if batched else dict(engine=engine)
@@ -54,7 +62,11 @@ def run_arm(n, p, arm, steps, prefix):
             s.set_pod_anti_affinity(True)
         s.load_nodes(nodes)
         s.save_table()
-        head = s.prepare(pods[:prefix])
+        try:
+            head = s.prepare(pods[:prefix])
+        except Exception as e:  # e.g. a tree from before QS_AA_SPREAD (--tree): the spread arms are skipped
+            out.update(skipped=str(e))
+            return out
         try:
             head.run(mode=mode)
         except Exception as e:  # e.g. PERSISTENT beyond its cap for this class
@@ -63,7 +75,9 @@ def run_arm(n, p, arm, steps, prefix):
             return out
         pl, keys = head.results()
         head.free()
-        if tracked or batched:
+        if spread:
+            ref = S.run(nodes, pods[:prefix])
+        elif tracked or batched:
             ref = A.run(nodes, pods[:prefix])
         else:
             on = {k: v.copy() for k, v in nodes.items()}
