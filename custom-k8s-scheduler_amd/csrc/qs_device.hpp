@@ -622,10 +622,16 @@ __device__ __forceinline__ uint32_t utilization_w(double a, double reqd, double 
 }
 
 // ---- spec S5/S6: QoS-weighted total of one feasible node ------------------------------------
-// floor(num / den) of a weighted mean of scores 0..100 (num = sum of score x weight < 2^24, den = the
-// weight sum < 2^18, num / den <= 100): the f32 estimate is within 100 * 2^-22 < 1 of num / den, so it
-// truncates to the floor or a neighbour; the exact remainder num - q den (|.| < 2^25) moves it by
-// one.  den == 0 (no resource counted) scores 0, as upstream's weightSum == 0.
+// floor(num / den) of a weighted mean of scores 0..100, or of its rounding form (2 num + den) / (2 den):
+// num < 2^25 (the legacy weights 65535 + 65535 give 2 * 13,107,000 + 131,070 = 26,345,070), den < 2^18,
+// num / den <= 100.5.  What is relied on: q within one of the floor, and |num - q den| < 2^31 for the
+// int32 remainder step that moves q by one.  The estimate: (float)num is within 2^-24 relative (exact
+// below 2^24), (float)den is exact (den < 2^24), v_rcp_f32 within 1 ulp (2^-23) and the product rounds
+// once more (2^-24), so the f32 quotient is within (num / den) * (2^-22 + 2^-45) of num / den: below 1
+// for every num / den < 2^21, here below 101 * 2^-22 < 2^-15, and it truncates to the floor or a
+// neighbour; q den <= 102 * 2^18 < 2^25 keeps the remainder below 2^26 in magnitude.  Run on the device
+// at num >= 2^24 by the `maxw` arm of tests/test_gpu_feature_fuzz.py.  den == 0 (no resource counted)
+// scores 0, as upstream's weightSum == 0.
 __device__ __forceinline__ uint32_t div_small(uint32_t num, uint32_t den) {
     const float d = (float)(den | (uint32_t)(den == 0u));
     int32_t q = (int32_t)((float)num * __builtin_amdgcn_rcpf(d));
