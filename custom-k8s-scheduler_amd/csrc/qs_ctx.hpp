@@ -148,6 +148,9 @@ struct qs_stream {
     // (above kSpreadApps the stream does not run PERSISTENT with tracking on)
     int32_t spread_row[qs::kMaxZones];
     uint32_t spread_apps = 0;
+    // per stream position (after the QoS sort): 1 = a QS_AA_SPREAD_SOFT pod (spec S14); the SCAN launch
+    // sequence gives such a pod the pre-pass in every class
+    std::vector<uint8_t> soft;
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
     // Uniform windows: run0[k] = first stream position of the run of byte-identical
@@ -189,6 +192,9 @@ struct qs_ctx {
     qs_scoring_strategy strat[3] = {};
     qs_host::DevBuf strat_tab;
     bool aa_track = false;  // required pod anti-affinity on the exact engines / score path (qs_set_pod_anti_affinity, spec S12)
+    int32_t w_pts = 2;  // PodTopologySpread plugin weight (qs_set_topology_spread_weight, spec S14; upstream's default)
+    int32_t score_zs[qs::kMaxZones];  // the zone scores of the last qs_score_pod call (qs_score_pod_zone_scores)
+    bool score_zs_valid = false;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

@@ -63,7 +63,10 @@ constexpr uint32_t kMaxApps = 1024, kMaxZones = 64, kAppWords = kMaxApps / 32;
 // Zone topology spread (spec S13): two more rows of kMaxZones words behind zcount[kMaxApps], the domain
 // flags (row kMaxApps) and the spread apps of a PERSISTENT stream (row kMaxApps + 1, kSpreadApps
 // entries, -1 = unused; the LDS slots of k_persistent).
-constexpr uint32_t kSpreadRows = 2, kSpreadApps = 64;
+// Zone topology spread scoring (spec S14): three more rows, written by the host wherever the domain
+// flags are: LOGTAB as 64 doubles (rows kMaxApps + 2 and + 3; entry D - 1 = RN(ln(D + 2))) and the
+// PodTopologySpread plugin weight Wpts (word 0 of row kMaxApps + 4).
+constexpr uint32_t kSpreadRows = 5, kSpreadApps = 64;
 static_assert(kSpreadApps <= kMaxZones, "the spread apps fill one row");
 struct DevTable {
     DRow *rows;       // compact layout (nullptr in the wide layout)
@@ -89,12 +92,16 @@ struct DevTable {
 // filter aa_ok below ANDed into feasibility and every placed pod recorded under its app.  The host
 // sets it, with kFeatExt, on every exact stream and qs_score_pod call of a context that tracks
 // anti-affinity (qs_set_pod_anti_affinity); its instantiations live in qs_kernels_aa.inc.
+// kFeatSoft (with kFeatAA) says that the stream holds soft-spread pods (spec S14).  No kernel is a
+// template over it: the host's dispatch picks the k_persistent instantiations that carry the score, and
+// their node caps, by it.
 enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u,
-                           kFeatStrat = 32u, kFeatAA = 64u };
+                           kFeatStrat = 32u, kFeatAA = 64u, kFeatSoft = 128u };
 
 // pod flags: bits 0-1 QoS, 2-3 the NodeResourcesFit strategy of the pod's QoS class (0 Least, 1 Most,
 // 2 RequestedToCapacityRatio; read by the kFeatStrat scorer only, every other reader masks its own
-// field), 4-6 required terms, 8-10 preferred terms, 12-13 anti-affinity kind,
+// field), 4-6 required terms, 8-10 preferred terms, 12-13 anti-affinity kind (0 for a soft-spread pod,
+// which no filter knows), 14 soft zone topology spread (spec S14; max_skew in bits 26-30 as for kind 3),
 // 16-25 app group (spec S11)
 __device__ __forceinline__ uint32_t pod_sid(uint32_t flags) { return (flags >> 2) & 3u; }
 __device__ __forceinline__ uint32_t pod_aa(uint32_t flags) { return (flags >> 12) & 3u; }

@@ -320,8 +320,51 @@ DRowW to_drow_wide(const HostRow &r) {
     return d;
 }
 
-// The two rows of spec S13 behind the (app, zone) counts: the domain flags from the mirror's zone
-// column, and an empty spread-app list (a PERSISTENT stream writes its own before it launches).
+// LOGTAB of spec S14: entry D - 1 is the IEEE double nearest to ln(D + 2), D = 1..64 (the topology
+// normalizing weight of UP podtopologyspread/scoring.go#topologyNormalizingWeight for D domains).
+// tests/golden/soft_spread_logtab.json holds the same 64 values; tests/test_soft_spread_cpu.py checks
+// them against an 80-digit evaluation.
+const double kLogTab[kMaxZones] = {
+    0x1.193ea7aad030bp+0, 0x1.62e42fefa39efp+0, 0x1.9c041f7ed8d33p+0, 0x1.cab0bfa2a2002p+0,
+    0x1.f2272ae325a57p+0, 0x1.0a2b23f3bab73p+1, 0x1.193ea7aad030bp+1, 0x1.26bb1bbb55516p+1,
+    0x1.32ee3b77f374cp+1, 0x1.3e116bcd39e7dp+1, 0x1.485042b318c51p+1, 0x1.51cca16d7bba7p+1,
+    0x1.5aa16394d481fp+1, 0x1.62e42fefa39efp+1, 0x1.6aa6bc1fa7f7ap+1, 0x1.71f7b3a6b9186p+1,
+    0x1.78e360604b32cp+1, 0x1.7f7427b73e391p+1, 0x1.85b2e946faeb1p+1, 0x1.8ba74773dc5c8p+1,
+    0x1.9157dfdd1b3f0p+1, 0x1.96ca77c922cf9p+1, 0x1.9c041f7ed8d33p+1, 0x1.a1094eaf01acdp+1,
+    0x1.a5ddfb8038490p+1, 0x1.aa85ad6964a23p+1, 0x1.af038cbcdfe1fp+1, 0x1.b35a6f90bd69bp+1,
+    0x1.b78ce48912b5ap+1, 0x1.bb9d3beb8c86bp+1, 0x1.bf8d8f4d5b8d1p+1, 0x1.c35fc81b90df6p+1,
+    0x1.c715a530ff3c5p+1, 0x1.cab0bfa2a2002p+1, 0x1.ce328ee3ac7bdp+1, 0x1.d19c6c5c341a8p+1,
+    0x1.d4ef968880dd6p+1, 0x1.d82d33b32720dp+1, 0x1.db565458eac4ep+1, 0x1.de6bf542e3d2dp+1,
+    0x1.e16f01614ec11p+1, 0x1.e460536fc5443p+1, 0x1.e740b76a3c9a4p+1, 0x1.ea10ebd90426cp+1,
+    0x1.ecd1a2f90f0b6p+1, 0x1.ef8383c50bb75p+1, 0x1.f2272ae325a57p+1, 0x1.f4bd2b7ac1bafp+1,
+    0x1.f7460ff5100ffp+1, 0x1.f9c25aaaea949p+1, 0x1.fc32868223cabp+1, 0x1.fe97077c2130cp+1,
+    0x1.0078259bafef3p+2, 0x1.019f5cb2a6c50p+2, 0x1.02c15a1ad9a59p+2, 0x1.03de4c5c6464dp+2,
+    0x1.04f65f9c72979p+2, 0x1.0609bdc65328bp+2, 0x1.07188eb126c0dp+2, 0x1.0822f8427dcebp+2,
+    0x1.09291e8e3181bp+2, 0x1.0a2b23f3bab73p+2, 0x1.0b29293942975p+2, 0x1.0c234da4a23a6p+2,
+};
+
+// The three rows of spec S14 behind the spread apps: LOGTAB and the plugin weight, as they go into
+// `rows` (3 * kMaxZones words).
+void fill_spread_cfg(const qs_ctx *c, int32_t *rows) {
+    static_assert(sizeof kLogTab == 2 * kMaxZones * 4 && kSpreadRows == 5, "LOGTAB fills two rows, the weight a third");
+    std::memset(rows, 0, 3 * kMaxZones * 4);
+    std::memcpy(rows, kLogTab, sizeof kLogTab);
+    rows[2 * kMaxZones] = c->w_pts;
+}
+// ... written alone by qs_set_topology_spread_weight and after qs_table_restore (whose snapshot holds
+// the weight of its save); every table upload writes them with the domain flags (write_domains).
+void write_spread_cfg(qs_ctx *c) {
+    if (!c->dt.zcount) return;
+    int32_t rows[3 * kMaxZones];
+    fill_spread_cfg(c, rows);
+    HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 2) * kMaxZones, rows, sizeof rows, hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (rows lives on this stack)
+}
+
+// The rows behind the (app, zone) counts in one copy: the two of spec S13, the domain flags from the
+// mirror's zone column and an empty spread-app list (a PERSISTENT stream writes its own before it
+// launches), and the three of spec S14.
 void write_domains(qs_ctx *c) {
     if (!c->dt.zcount) return;
     int32_t rows[kSpreadRows * kMaxZones];
@@ -330,6 +373,7 @@ void write_domains(qs_ctx *c) {
         rows[z] = (int32_t)((dom >> z) & 1u);
         rows[kMaxZones + z] = -1;
     }
+    fill_spread_cfg(c, rows + 2 * kMaxZones);
     HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)kMaxApps * kMaxZones, rows, sizeof rows, hipMemcpyHostToDevice,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // (rows lives on this stack)
@@ -481,25 +525,30 @@ void check_pod(const qs_pod &p, uint32_t j) {
     const int32_t kind = QS_AA_KIND(p.anti_affinity);
     if (p.anti_affinity < 0 || kind > QS_AA_SPREAD_ZONE) bad("anti_affinity kind must be 0..3");
     if (kind == QS_AA_SPREAD_ZONE) {
-        const int32_t skew = p.anti_affinity >> 8;
+        // ... and QS_AA_SOFT above it (spec S14), the only bit above max_skew
+        const int32_t skew = (p.anti_affinity & ~QS_AA_SOFT) >> 8;
         if (skew < 1 || skew > QS_MAX_SPREAD_SKEW) bad("anti_affinity: max_skew of QS_AA_SPREAD must be 1..31");
     } else if (p.anti_affinity != kind) {
-        bad("anti_affinity: bits above the kind must be zero (only QS_AA_SPREAD carries max_skew)");
+        bad("anti_affinity: bits above the kind must be zero (only QS_AA_SPREAD carries max_skew and QS_AA_SOFT)");
     }
 }
+// (a soft-spread pod too, spec S14: k_persistent needs its app's counts like a SPREAD pod's)
 bool pod_spreads(const qs_pod &p) { return QS_AA_KIND(p.anti_affinity) == QS_AA_SPREAD_ZONE; }
+bool pod_soft_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_SOFT(p.anti_affinity); }
 
 // NodeAffinity disabled (config.enable_affinity = 0): the pod's required / preferred term counts are
 // recorded as 0, so the normalizing kernels (which evaluate both plugins) neither filter nor score
 // by affinity.  Bits 2-3: the strategy of the pod's QoS class (qs_scoring_strategy_type), which only
 // the kFeatStrat scorer reads (check_pod has bounded qos to 0..2).  Bits 12-13: the anti-affinity kind;
 // bits 26-30: max_skew of a QS_AA_SPREAD pod (0 for every other kind; spec S13, read by the kFeatAA
-// kernels only).  Bit 31 stays the batched claim's.
+// kernels only).  Bit 31 stays the batched claim's.  A QS_AA_SPREAD_SOFT pod (spec S14) carries kind 0,
+// so that no filter knows it, bit 14, and its max_skew.
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
+    const bool soft = pod_soft_spread(p);
     return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
-           (aff * (uint32_t)p.n_pref_terms << 8) | ((uint32_t)QS_AA_KIND(p.anti_affinity) << 12) |
-           ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
+           (aff * (uint32_t)p.n_pref_terms << 8) | ((soft ? 0u : (uint32_t)QS_AA_KIND(p.anti_affinity)) << 12) |
+           ((soft ? 1u : 0u) << 14) | ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
 }
 
 // Device pod record in the context's layout: DPod (compact, memory in 2^shift units) or DPodW
@@ -764,7 +813,7 @@ int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false) {
         // persistent workgroup keeps counts for (kSpreadApps) runs SCAN, like a table
         // above the node cap
         if (spread_over && e == QS_ENGINE_PERSISTENT)
-            fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD pods of at most " + std::to_string(kSpreadApps) +
+            fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD / QS_AA_SPREAD_SOFT pods of at most " + std::to_string(kSpreadApps) +
                                 " distinct apps per stream");
         if (e == QS_ENGINE_AUTO)
             e = n <= persistent_max_nodes(feat) && !spread_over ? QS_ENGINE_PERSISTENT : QS_ENGINE_SCAN;
@@ -1126,6 +1175,34 @@ qs_status qs_get_pod_anti_affinity(qs_ctx *c, int32_t *on) {
         if (!on) fail(QS_EINVAL, "null output");
         *on = c->aa_track ? 1 : 0;
     });
+}
+
+qs_status qs_set_topology_spread_weight(qs_ctx *c, int32_t w) {
+    return guarded(c, [&] {
+        if (!c->streams.empty())
+            fail(QS_ESTATE, "the topology spread weight cannot change while prepared streams exist");
+        if (w < 0 || w > 100) fail(QS_EINVAL, "the topology spread weight must be 0..100");
+        c->w_pts = w;
+        if (c->dev_valid) {
+            HIPCHK(hipSetDevice(c->device));
+            write_spread_cfg(c);
+        }
+    });
+}
+
+qs_status qs_get_topology_spread_weight(qs_ctx *c, int32_t *w) {
+    return guarded(c, [&] {
+        if (!w) fail(QS_EINVAL, "null output");
+        *w = c->w_pts;
+    });
+}
+
+qs_status qs_score_pod_zone_scores(qs_ctx *c, int32_t *out) {
+    return guarded(c, [&] {
+        if (!out) fail(QS_EINVAL, "null output");
+        if (!c->score_zs_valid) fail(QS_ESTATE, "no qs_score_pod / qs_score_pod_packed call yet");
+        std::memcpy(out, c->score_zs, sizeof c->score_zs);
+    }, /*keep_pending=*/true);
 }
 
 // (no context: why the calling thread's last qs_open / qs_open_shard failed, or "null context")
@@ -1495,8 +1572,10 @@ static void score_diag_report(uint64_t seq, std::chrono::steady_clock::time_poin
                      (unsigned long long)seq, us(s.ts, s.tl), us(s.tl, s.t0), us(s.t0, s.te), us(s.te, tu));
 }
 
-static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t wts[4], int32_t *best) {
+static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t wts[5], int32_t *best) {
     if (g_sdiag) g_split.ts = std::chrono::steady_clock::now();
+    // qs_score_pod_zone_scores answers for the last call, once it has succeeded: void until then
+    c->score_zs_valid = false;
     if (!pod) fail(QS_EINVAL, "null pod");
     HIPCHK(hipSetDevice(c->device));
     check_pod(*pod, 0);
@@ -1524,12 +1603,17 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
     }
     wts[2] = (dc.feat & kFeatTaint) ? (uint32_t)dc.wtt : 0u;
     wts[3] = (dc.feat & kFeatAffinity) ? (uint32_t)dc.wna : 0u;
+    std::fill(std::begin(c->score_zs), std::end(c->score_zs), -1);
+    wts[4] = 0u;
     if (n == 0 || !c->dev_valid) {
         if (best) *best = -1;
+        c->score_zs_valid = true;
         return nullptr;
     }
     const DPodX dx = compact_podx(c, *pod);
-    const size_t pb = score_pod1_pack_bytes(n);
+    // (behind the packed words: the 64 zone scores of a soft-spread pod, spec S14)
+    const size_t pb = score_pod1_pack_bytes(n) + kMaxZones * 4;
+    const bool soft = c->aa_track && pod_soft_spread(*pod);
     if (c->pin_bytes < pb) {
         if (c->pin) (void)hipHostFree(c->pin);
         c->pin = nullptr;
@@ -1539,8 +1623,8 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
         std::memset(c->pin, 0, pb);
     }
     if (!c->score_gs.p) {
-        c->score_gs.ensure(32);
-        HIPCHK(hipMemsetAsync(c->score_gs.p, 0, 32, c->stream));
+        c->score_gs.ensure(64);  // (+ the feasible-zones word of a soft-spread pod)
+        HIPCHK(hipMemsetAsync(c->score_gs.p, 0, 64, c->stream));
     }
     const uint32_t pidx = c->pend < n ? c->pend : 0xFFFFFFFFu;
     const HostRow prow = pidx < n ? compact_row(c->m, pidx, c->shift, c->wide) : HostRow{};
@@ -1569,22 +1653,31 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
     uint64_t kbest = 0;
     std::memcpy(&kbest, h, 8);
     if (best) *best = kbest ? (int32_t)(0xFFFFFFFFu - (uint32_t)kbest) : -1;
+    if (soft) std::memcpy(c->score_zs, h + score_pod1_pack_bytes(n), sizeof c->score_zs);
+    c->score_zs_valid = true;
+    wts[4] = soft ? (uint32_t)c->w_pts : 0u;
     return reinterpret_cast<const uint32_t *>(h + 16);
 }
 
 qs_status qs_score_pod(qs_ctx *c, const qs_pod *pod, uint8_t *feas, int32_t *score, int32_t *total,
                        int32_t *best) {
     return guarded(c, [&] {
-        uint32_t w[4];
+        uint32_t w[5];
         const uint32_t *pk = score_pod_launch(c, pod, w, best);
         if (pk) unpack_scores(pk, c->m.n, w, feas, score, total);
+        if (pk && total && w[4]) {
+            // a soft-spread pod (spec S14): the fifth score by the node's zone (a feasible node's zone
+            // holds a feasible node, so its score is there)
+            for (uint32_t i = 0; i < c->m.n; i++)
+                if (total[i] >= 0) total[i] += (int32_t)w[4] * std::max(c->score_zs[c->m.zone[i]], 0);
+        }
         if (g_sdiag && pk) score_diag_report(c->score_seq, std::chrono::steady_clock::now());
     }, /*keep_pending=*/true);
 }
 
 qs_status qs_score_pod_packed(qs_ctx *c, const qs_pod *pod, const uint32_t **packed, int32_t *best) {
     return guarded(c, [&] {
-        uint32_t w[4];
+        uint32_t w[5];
         const uint32_t *pk = score_pod_launch(c, pod, w, best);
         if (packed) *packed = pk;
         if (g_sdiag && pk) score_diag_report(c->score_seq, std::chrono::steady_clock::now());
@@ -1627,8 +1720,10 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         std::vector<uint8_t> dp(rb * std::max<uint32_t>(p, 1));
         const bool needx = feat_of(c->cfg) & (kFeatTaint | kFeatAffinity);
         std::vector<DPodX> dx(needx ? std::max<uint32_t>(p, 1) : 1);
+        s->soft.assign(p, 0);
         for (uint32_t k = 0; k < p; k++) {
             const uint32_t j = s->order[k];
+            s->soft[k] = pod_soft_spread(pods[j]) ? 1 : 0;
             compact_pod(c, pods[j], j, c->shift, c->wide, dp.data() + rb * k);
             if (needx) dx[k] = compact_podx(c, pods[j]);
         }
@@ -1663,7 +1758,7 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         if (mode != QS_MODE_EXACT && mode != QS_MODE_BATCHED) fail(QS_EINVAL, "unknown qs_mode");
         if (s->shift != c->shift || s->wide != c->wide) fail(QS_ESTATE, "node table re-laid out after prepare");
         if (mode == QS_MODE_BATCHED && s->spread_apps != 0)
-            fail(QS_EINVAL, "QS_MODE_BATCHED does not know zone topology spread (QS_AA_SPREAD pods, spec S13): "
+            fail(QS_EINVAL, "QS_MODE_BATCHED does not know zone topology spread (QS_AA_SPREAD / QS_AA_SPREAD_SOFT pods, spec S13, S14): "
                             "run the stream in QS_MODE_EXACT on a context that tracks pod anti-affinity");
         HIPCHK(hipSetDevice(c->device));
         // from here on the device table (and d_node) may change even if this run fails part way
@@ -1681,7 +1776,11 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         // and records its pods; batched mode filters and records by itself (S11, the same state)
         const bool aa_exact = c->aa_track && mode == QS_MODE_EXACT;
         if (c->aa_track) aa_check_table(c);
-        if (aa_exact) c->dc.feat = aa_feat(s->feat);
+        if (aa_exact) {
+            c->dc.feat = aa_feat(s->feat);
+            // soft-spread pods (spec S14): the k_persistent instantiations that carry the score, and their caps
+            if (std::find(s->soft.begin(), s->soft.end(), 1) != s->soft.end()) c->dc.feat |= kFeatSoft;
+        }
         // zone topology spread (spec S13): k_persistent keeps the counts of at most kSpreadApps apps
         const bool spread_over = aa_exact && s->spread_apps > kSpreadApps;
         const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n, spread_over);
@@ -1715,12 +1814,14 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                 HIPCHK(hipMemsetAsync(c->scratch.p, 0, scan_scratch_bytes(), c->stream));
                 ensure_soa(c);
                 for (uint32_t k = 0; k < P; k++) {
+                    // (128: a soft-spread pod of a tracked stream, spec S14: the pre-pass in every class)
+                    const int sp = aa_exact && s->soft[k] ? 128 : 0;
                     kt.begin(1, c->stream);  // the key scan alone (+ normalize pre-pass)
                     HIPCHK(launch_scan_pod(c->dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st,
-                                           nullptr, nullptr, nullptr, 1, c->stream));
+                                           nullptr, nullptr, nullptr, 1 | sp, c->stream));
                     kt.end(1, c->stream);
                     HIPCHK(launch_scan_pod(c->dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st,
-                                           nullptr, nullptr, nullptr, 2, c->stream));
+                                           nullptr, nullptr, nullptr, 2 | sp, c->stream));
                 }
                 batches = P;
             } else if (eng == QS_ENGINE_ALLREDUCE) {
@@ -2345,6 +2446,7 @@ qs_status qs_table_restore(qs_ctx *c) {
             fail(QS_ESTATE, "no matching qs_table_save snapshot");
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipMemcpyAsync(c->tbl.p, c->tbl_saved.p, c->tbl.bytes, hipMemcpyDeviceToDevice, c->stream));
+        write_spread_cfg(c);      // (the snapshot holds the topology spread weight of its save)
         c->m = c->m_saved;        // the mirror of the snapshot
         c->zero_alloc = count_zero_alloc(c->m);
         c->mirror_stale = false;

@@ -100,7 +100,83 @@ __device__ __forceinline__ uint8_t *aa_lds_slot() {
     return slot;
 }
 
-template <int NPT, int BS, uint32_t F>
+// Zone topology spread scoring (soft spread, spec S14; pod-flag bit 14, the kind bits of such a pod are
+// 0 so no filter sees it).  Per pod: the feasible-zones word fz (OR of 1 << zone(i) over the nodes that
+// pass the pod's filters: a reduction of its own, beside the normalize maxima), then once per wave the
+// score of every zone with lane z holding zone z, then a lookup by the node's zone.  LOGTAB and Wpts
+// sit in the rows behind the spread apps (qs_device.hpp).
+__host__ __device__ __forceinline__ bool pod_soft(uint32_t flags) { return ((flags >> 14) & 1u) != 0; }
+__device__ __forceinline__ const double *aa_logtab(const DevTable &t) {
+    return reinterpret_cast<const double *>(t.zcount + (kMaxApps + 2) * kMaxZones);
+}
+__device__ __forceinline__ uint32_t aa_wpts(const DevTable &t) { return (uint32_t)t.zcount[(kMaxApps + 4) * kMaxZones]; }
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ uint32_t dpp_or32(uint32_t v) { return v | dpp32<CTRL, ROW_MASK>(v); }
+// Full-wave OR (the steps of wave_max_u32); every lane must be active.  Wave-uniform.
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
+    v = dpp_or32<0xB1>(v);
+    v = dpp_or32<0x4E>(v);
+    v = dpp_or32<0x141>(v);
+    v = dpp_or32<0x140>(v);
+    v = dpp_or32<0x142, 0xA>(v);
+    v = dpp_or32<0x143, 0xC>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) {
+    return ((uint64_t)wave_or_u32((uint32_t)(v >> 32)) << 32) | wave_or_u32((uint32_t)v);
+}
+constexpr uint32_t kNoZoneScore = 0xFFu;  // a zone outside Z
+// PTS of zone z in lane z (0..100; kNoZoneScore where z holds no feasible node); every lane of the wave
+// must be active.  cz = the app's recorded pods in zone z (>= 0), fz != 0 the feasible-zones word, skew
+// = max_skew (>= 1), w = LOGTAB[D].  x = RN(RN(c * w) + t) with two roundings (__dmul_rn / __dadd_rn: no
+// fused multiply-add whatever the contraction mode), raw = floor(x + 0.5) (x + 0.5 is exact below 2^52),
+// minimum and maximum over Z as two wave maxima of 64-bit words, and the integer quotient
+// floor(100 (mx + mn - raw) / mx) <= 100 from the f64 quotient of two integers below 2^43, corrected
+// in integers.
+__device__ __forceinline__ uint32_t soft_zone_score(int32_t cz, uint64_t fz, uint32_t skew, const double *logtab) {
+    const uint32_t z = threadIdx.x & 63u;
+    const bool in = ((fz >> z) & 1ull) != 0;
+    const uint32_t D = (uint32_t)__popcll(fz);
+    const double w = logtab[(D ? D : 1u) - 1u];
+    const double x = __dadd_rn(__dmul_rn((double)cz, w), (double)(skew - 1u));
+    const uint64_t raw = (uint64_t)(x + 0.5);
+    const uint64_t mx = wave_max_u64(in ? raw : 0ull);
+    const uint64_t mn = ~wave_max_u64(in ? ~raw : 0ull);
+    if (!in) return kNoZoneScore;
+    if (mx == 0) return 100u;
+    const uint64_t a = 100ull * (mx + mn - raw);
+    uint64_t q = (uint64_t)((double)a / (double)mx);
+    if (q * mx > a) --q;
+    if ((q + 1) * mx <= a) ++q;
+    return (uint32_t)q;
+}
+// One byte per zone and wave for the kernels whose node loops diverge (SCAN, the score path): a
+// ds_bpermute under a divergent mask reads 0 from inactive lanes, LDS does not.
+template <int NW>
+__device__ __forceinline__ uint8_t *aa_lds_zscore() {
+    __shared__ uint8_t zs[NW][kMaxZones];
+    return zs[threadIdx.x >> 6];
+}
+// The wave's zone scores of a soft pod from the global counts (SCAN and the score path; the counts of
+// the pod's turn and fz are a kernel boundary behind) into the wave's LDS bytes; nullptr for every
+// other pod.  Call it with every lane active.  The returned bytes are read by this wave only.
+template <int NW>
+__device__ __forceinline__ const uint8_t *soft_zone_bytes(const DevTable &t, uint32_t flags, uint64_t fz) {
+    if (!pod_soft(flags)) return nullptr;
+    uint8_t *zs = aa_lds_zscore<NW>();
+    const uint32_t z = threadIdx.x & 63u;
+    const int32_t cz = t.zcount[pod_app(flags) * kMaxZones + z];
+    zs[z] = (uint8_t)(fz ? soft_zone_score(cz, fz, pod_skew(flags), aa_logtab(t)) : kNoZoneScore);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return zs;
+}
+
+// SOFT (kFeatAA classes only): the instantiation of a stream that holds soft-spread pods (spec S14,
+// kFeatSoft), with node caps of its own (persistent_cap); every other stream runs the code it ran
+// before the score existed.
+template <int NPT, int BS, uint32_t F, bool SOFT = false>
 __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__restrict__ pods,
                                                    const DPodX *__restrict__ podx, uint32_t P,
                                                    DevCfg c, int32_t *__restrict__ out_node,
@@ -109,6 +185,15 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
     constexpr int NW = BS / kWave;
     __shared__ uint64_t red[2][NW];
     __shared__ uint32_t redn[2][2][NW];
+    // soft-spread pods (spec S14): the waves' feasible-zones words, by the pod's parity like redn
+    // and the zone scores, a byte per zone and wave (each wave computes and reads its own)
+    [[maybe_unused]] uint64_t (*redz)[NW] = nullptr;
+    [[maybe_unused]] uint8_t *zsb = nullptr;
+    if constexpr ((F & kFeatAA) != 0 && SOFT) {
+        __shared__ uint64_t rz[2][NW];
+        redz = rz;
+        zsb = aa_lds_zscore<NW>();
+    }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t n = t.n;
     RowT<F> r[NPT];
@@ -225,12 +310,22 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
         }
         uint32_t mt = 0, ma = 0;
         double ymt = 0.0, yma = 0.0;
+        // soft-spread pods (spec S14; the pod record is workgroup-uniform, so is every branch on it):
+        // the zones of the lane's feasible nodes, reduced over the workgroup beside the maxima
+        // (each node's word is reduced over the wave at once, into scalar registers: no vector register
+        // lives across the loop for it)
+        [[maybe_unused]] bool soft = false;
+        [[maybe_unused]] uint64_t lz = 0;
+        if constexpr ((F & kFeatAA) != 0 && SOFT) soft = pod_soft(p.flags);
         if (F & kFeatNorm) {  // NormalizeScore maxima over feasible nodes (spec S5)
             uint32_t lt = 0, la = 0;
 #pragma unroll
             for (int k = 0; k < NPT; ++k) {
                 bool f = feasible<F>(r[k], x[k], p, px);
                 if constexpr ((F & kFeatAA) != 0) f &= ((aam >> k) & 1u) != 0;
+                if constexpr ((F & kFeatAA) != 0 && SOFT) {
+                    if (soft) lz |= wave_or_u64(f ? 1ull << zn[k] : 0ull);
+                }
                 const uint32_t a = f ? taint_raw(x[k], px) : 0u;
                 const uint32_t b = f ? affinity_raw(x[k], p, px) : 0u;
                 lt = a > lt ? a : lt;
@@ -239,6 +334,9 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
             lt = wave_max_u32(lt);
             la = wave_max_u32(la);
             if (lane == 0) { redn[s & 1][0][w] = lt; redn[s & 1][1][w] = la; }
+            if constexpr ((F & kFeatAA) != 0 && SOFT) {
+                if (soft && lane == 0) redz[s & 1][w] = lz;
+            }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < NW; ++i) {
@@ -249,12 +347,46 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
             ymt = rcp_exact(mt);
             yma = rcp_exact(ma);
         }
+        [[maybe_unused]] uint32_t wpts = 0;  // Wpts (wave-uniform)
+        if constexpr ((F & kFeatAA) != 0 && SOFT) {
+            if (soft) {
+                if constexpr ((F & kFeatNorm) == 0) {
+                    // the classes without a normalizing plugin have no pre-pass: one for this pod,
+                    // with a barrier of its own
+#pragma unroll
+                    for (int k = 0; k < NPT; ++k) {
+                        const bool f = feasible<F>(r[k], x[k], p, px) && ((aam >> k) & 1u) != 0;
+                        lz |= wave_or_u64(f ? 1ull << zn[k] : 0ull);
+                    }
+                    if (lane == 0) redz[s & 1][w] = lz;
+                    __syncthreads();
+                }
+                uint64_t fz = 0;
+#pragma unroll
+                for (int i = 0; i < NW; ++i) fz |= redz[s & 1][i];
+                // the counts as a SPREAD pod reads them (above): copy s & 1 plus the previous pod's own
+                // +1 from the registers; every lane is active, lane z holds zone z
+                const uint32_t sl = slot[pod_app(p.flags)];
+                int32_t cz = spc[((s & 1u) * kSpreadApps + (sl & (kSpreadApps - 1u))) * kMaxZones + lane];
+                cz += (pod_app(p.flags) == prev_app && ((prev_bit >> lane) & 1ull)) ? 1 : 0;
+                cz = sl < kSpreadApps ? cz : 0;
+                // (the wave's own bytes: its reads of the previous soft pod's are behind it in program order)
+                zsb[lane] = (uint8_t)(fz ? soft_zone_score(cz, fz, pod_skew(p.flags), aa_logtab(t)) : kNoZoneScore);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wpts = aa_wpts(t);
+            }
+        }
         uint64_t best = 0;
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             bool f = feasible<F>(r[k], x[k], p, px);
             if constexpr ((F & kFeatAA) != 0) f &= ((aam >> k) & 1u) != 0;
-            const uint32_t tot = node_total<F>(r[k], x[k], p, px, c, mt, ymt, ma, yma, nullptr);
+            uint32_t tot = node_total<F>(r[k], x[k], p, px, c, mt, ymt, ma, yma, nullptr);
+            if constexpr ((F & kFeatAA) != 0 && SOFT) {
+                if (soft) tot += wpts * (uint32_t)zsb[zn[k]];  // (an infeasible node's total is not used)
+            }
             const uint64_t key = f ? pack_key(tot + 1, tid + k * BS) : 0ull;
             best = key > best ? key : best;
         }
@@ -338,6 +470,9 @@ struct ScanScratch {
     uint32_t lo, hi;          // node range the row scans cover (hi == 0: the whole table); a rank's
                               // shard for the per-pod all-reduce engine (QS_ENGINE_ALLREDUCE)
     uint64_t partial[kScanBlocksMax];
+    // soft-spread pods (spec S14): the feasible-zones word of k_scan_norm, reset with mt / ma.  Behind
+    // the partials, so that every older member stays where the kernels without kFeatAA address it.
+    unsigned long long fz;
 };
 static_assert(offsetof(ScanScratch, lo) == offsetof(ScanHead, lo) && offsetof(ScanScratch, mt) == offsetof(ScanHead, mt),
               "ScanHead mirrors ScanScratch");
@@ -360,10 +495,17 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
                                                    const DPodX *__restrict__ podx, uint32_t s,
                                                    ScanScratch *sc) {
     const PodT<F> p = pods[s];
-    const DPodX px = podx[s];
+    // (a kFeatAA class without the normalizing plugins runs this pre-pass for soft-spread pods only,
+    // spec S14, and has no extension records)
+    const DPodX px = [&] {
+        if constexpr ((F & kFeatAA) != 0 && (F & kFeatNorm) == 0) return DPodX{};
+        else return podx[s];
+    }();
     uint32_t lt = 0, la = 0;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
-    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
+    [[maybe_unused]] uint64_t lz = 0;      // soft-spread pods: the zones of this lane's feasible nodes (spec S14)
+    [[maybe_unused]] bool soft = false;
+    if constexpr ((F & kFeatAA) != 0) { zw = spread_word(t, p.flags); soft = pod_soft(p.flags); }
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
@@ -374,14 +516,23 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
             const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
             lt = a > lt ? a : lt;
             la = b > la ? b : la;
+            if constexpr ((F & kFeatAA) != 0) {
+                if (soft) lz |= 1ull << (uint32_t)t.zone[i];
+            }
         }
     }
     // (normalizing profiles run this scan on row tables of a few thousand nodes: few blocks)
     lt = wave_max_u32(lt);
     la = wave_max_u32(la);
+    if constexpr ((F & kFeatAA) != 0) {
+        if (soft) lz = wave_or_u64(lz);  // (the loop is over: every lane is active again)
+    }
     if ((threadIdx.x & 63) == 0) {
         if (lt) atomicMax(&sc->mt, lt);
         if (la) atomicMax(&sc->ma, la);
+        if constexpr ((F & kFeatAA) != 0) {
+            if (lz) atomicOr(&sc->fz, (unsigned long long)lz);  // one per wave
+        }
     }
 }
 
@@ -398,7 +549,14 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
     const double ymt = rcp_exact(mt), yma = rcp_exact(ma);
     uint64_t best = 0;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
-    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
+    // soft-spread pods (spec S14): the wave's zone scores from k_scan_norm's word, and the plugin weight
+    [[maybe_unused]] const uint8_t *zs = nullptr;
+    [[maybe_unused]] uint32_t wpts = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        zw = spread_word(t, p.flags);
+        zs = soft_zone_bytes<4>(t, p.flags, pod_soft(p.flags) ? sc->fz : 0ull);
+        if (zs) wpts = aa_wpts(t);
+    }
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
@@ -408,8 +566,12 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
         uint32_t sco[4];
         // (kFeatAA classes: the scores always go to the local array, which then stays in registers;
         // the pointer select of the older classes keeps their heavier scorers' array in scratch)
-        const uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma,
-                                           ((F & kFeatAA) != 0 || score_out) ? sco : nullptr);
+        uint32_t tot = node_total<F>(r, x, p, px, c, mt, ymt, ma, yma,
+                                     ((F & kFeatAA) != 0 || score_out) ? sco : nullptr);
+        if constexpr ((F & kFeatAA) != 0) {
+            // (an infeasible node may read kNoZoneScore: its total is not used)
+            if (zs) tot += wpts * (uint32_t)zs[(uint32_t)t.zone[i]];
+        }
         const uint64_t key = f ? pack_key(tot + 1, i) : 0ull;
         best = key > best ? key : best;
         if (feas_out) feas_out[i] = f;
@@ -521,6 +683,7 @@ __global__ __launch_bounds__(256) void k_scan_commit(DevTable t, const PodT<F> *
     sc->best = nblk ? ks : 0ull;
     sc->mt = 0;
     sc->ma = 0;
+    if constexpr ((F & kFeatAA) != 0) sc->fz = 0;
     if (!out_node) return;
     const PodT<F> p = pods[s];
     if (ks) {
@@ -687,10 +850,11 @@ constexpr uint32_t kScorePodGT = 1024;  // (fewer workgroups: fewer arrivals on 
 template <uint32_t F>
 __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT<F> p, DPodX px, uint64_t *gs,
                                                                 uint32_t pidx, HostRow prow) {
-    static_assert((F & kFeatNorm) != 0, "maxima of the normalizing plugins only");
+    static_assert((F & (kFeatNorm | kFeatAA)) != 0, "maxima of the normalizing plugins, or a soft-spread pod's zones");
     const uint32_t n = t.n, i = blockIdx.x * kScorePodGT + threadIdx.x;
     uint32_t mt = 0, ma = 0;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
+    [[maybe_unused]] uint64_t lz = 0;      // soft-spread pods: the zone of this lane's node if feasible (spec S14)
     if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
     if (i < n) {
         RowT<F> r;
@@ -706,13 +870,23 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
         if (f) {
             mt = taint_raw(x, px);
             ma = affinity_raw(x, p, px);
+            if constexpr ((F & kFeatAA) != 0) {
+                // (the pending row's zone is the table's: a Reserve does not move a node)
+                if (pod_soft(p.flags)) lz = 1ull << (uint32_t)(i == pidx ? prow.zone : t.zone[i]);
+            }
         }
     }
     mt = wave_max_u32(mt);
     ma = wave_max_u32(ma);
+    if constexpr ((F & kFeatAA) != 0) {
+        if (pod_soft(p.flags)) lz = wave_or_u64(lz);
+    }
     if ((threadIdx.x & 63) == 0) {  // one atomic per wave (words stay zero between calls)
         if (mt) __hip_atomic_fetch_max(gs + 2, (uint64_t)mt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (ma) __hip_atomic_fetch_max(gs + 3, (uint64_t)ma, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr ((F & kFeatAA) != 0) {
+            if (lz) __hip_atomic_fetch_or(gs + 4, lz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 template <uint32_t F>
@@ -724,7 +898,21 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
     const uint32_t n = t.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t i = blockIdx.x * kScorePodGT + tid;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
-    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
+    // soft-spread pods (spec S14): the wave's zone scores from k_score_podg_max's word (gs[4]), the plugin
+    // weight, and the scores themselves as 64 int32 behind the packed words (-1 = no feasible node)
+    [[maybe_unused]] const uint8_t *zs = nullptr;
+    [[maybe_unused]] uint32_t wpts = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        zw = spread_word(t, p.flags);
+        uint64_t fz = 0;
+        if (pod_soft(p.flags)) fz = __hip_atomic_load(gs + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        zs = soft_zone_bytes<NW>(t, p.flags, fz);
+        if (zs) {
+            wpts = aa_wpts(t);
+            if (blockIdx.x == 0 && wv == 0)
+                reinterpret_cast<int32_t *>(hout + score_pack_bytes(n))[lane] = zs[lane] == kNoZoneScore ? -1 : (int32_t)zs[lane];
+        }
+    }
     if (blockIdx.x == 0 && tid == 0 && pidx < n) set_row(t, pidx, prow);
     uint32_t mt = 0, ma = 0;
     if constexpr ((F & kFeatNorm) != 0) {  // k_score_podg_max's maxima (the previous launch)
@@ -744,7 +932,10 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
         bool f = feasible<F>(r, x, p, px);
         if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
         uint32_t sco[4];
-        const uint32_t tot = node_total<F>(r, x, p, px, c, mt, rcp_exact(mt), ma, rcp_exact(ma), sco);
+        uint32_t tot = node_total<F>(r, x, p, px, c, mt, rcp_exact(mt), ma, rcp_exact(ma), sco);
+        if constexpr ((F & kFeatAA) != 0) {
+            if (zs) tot += wpts * (uint32_t)zs[(uint32_t)(i == pidx ? prow.zone : t.zone[i])];
+        }
         best = f ? pack_key(tot + 1, i) : 0ull;
         reinterpret_cast<uint32_t *>(hout + 16)[i] = pack_scores(f, sco);
     }
@@ -768,6 +959,7 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
                 __hip_atomic_store(gs + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(gs + 3, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            if constexpr ((F & kFeatAA) != 0) __hip_atomic_store(gs + 4, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             *reinterpret_cast<volatile uint64_t *>(hout) = b;
             __threadfence_system();
             __hip_atomic_store(reinterpret_cast<uint64_t *>(hout + 8), seq, __ATOMIC_RELEASE,
@@ -4573,11 +4765,11 @@ __global__ __launch_bounds__(64 * kClaimWaves) void k_batch_claim(
 // =============================================================================================
 #define QS_RET(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-template <int NPT, int BS, uint32_t F>
+template <int NPT, int BS, uint32_t F, bool SOFT = false>
 static hipError_t persistent_t(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st,
                                hipStream_t stream) {
-    hipLaunchKernelGGL((k_persistent<NPT, BS, F>), dim3(1), dim3(BS), 0, stream, t,
+    hipLaunchKernelGGL((k_persistent<NPT, BS, F, SOFT>), dim3(1), dim3(BS), 0, stream, t,
                        (const PodT<F> *)pods, podx, P, c, on, ok, st);
     return hipGetLastError();
 }
@@ -4585,11 +4777,17 @@ static hipError_t persistent_t(const DevTable &t, const void *pods, const DPodX 
 // Largest node count per feature set for the register-resident rows (1024 threads, 4 waves/SIMD;
 // the largest NPT of each set spills a few dwords to scratch: correct, slower — the LOOKAHEAD
 // engine is the fast path at these sizes).  Wide rows carry three f64 memory columns.
-template <uint32_t F>
+template <uint32_t F, bool SOFT = false>
 static constexpr uint32_t persistent_cap() {
     // anti-affinity classes (kFeatAA): a zone register per node beside the rows, and no spill at all
     // (tests/test_antiaffinity_cpu.py reads the code objects): see DESIGN.md §3.4 for the budget
     if (F & kFeatAA) {
+        // the instantiations with the soft-spread score (spec S14): the caps at which they too are
+        // without spill (tests/test_soft_spread_cpu.py)
+        if (SOFT) {
+            if (F & kFeatWide) return (F & kFeatNorm) ? 1024u : 2048u;
+            return (F & kFeatNorm) ? 1024u : (F & kFeatRes) ? 2048u : 3072u;
+        }
         if (F & kFeatWide) return (F & kFeatNorm) ? 1024u : 2048u;
         return (F & (kFeatNorm | kFeatRes)) ? 2048u : 3072u;
     }
@@ -4597,31 +4795,31 @@ static constexpr uint32_t persistent_cap() {
     return F == 0 ? 6144u : (F == kFeatExt ? 5120u : 2048u);
 }
 
-template <uint32_t F>
+template <uint32_t F, bool SOFT = false>
 static hipError_t persistent_f(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st,
                                hipStream_t stream) {
     const uint32_t n = t.n;
-    if (n > persistent_cap<F>()) return hipErrorInvalidValue;
-    if (n <= 64) return persistent_t<1, 64, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 128) return persistent_t<1, 128, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 256) return persistent_t<1, 256, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 512) return persistent_t<1, 512, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 1024) return persistent_t<1, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
-    if constexpr (persistent_cap<F>() > 1024) {
-        if (n <= 2048) return persistent_t<2, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n > persistent_cap<F, SOFT>()) return hipErrorInvalidValue;
+    if (n <= 64) return persistent_t<1, 64, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 128) return persistent_t<1, 128, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 256) return persistent_t<1, 256, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 512) return persistent_t<1, 512, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 1024) return persistent_t<1, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT>() > 1024) {
+        if (n <= 2048) return persistent_t<2, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F>() > 2048) {
-        if (n <= 3072) return persistent_t<3, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT>() > 2048) {
+        if (n <= 3072) return persistent_t<3, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F>() > 3072) {
-        if (n <= 4096) return persistent_t<4, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT>() > 3072) {
+        if (n <= 4096) return persistent_t<4, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F>() > 4096) {
-        if (n <= 5120) return persistent_t<5, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT>() > 4096) {
+        if (n <= 5120) return persistent_t<5, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F>() > 5120) {
-        if (n <= 6144) return persistent_t<6, 1024, F>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT>() > 5120) {
+        if (n <= 6144) return persistent_t<6, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
     }
     return hipErrorInvalidValue;
 }
@@ -4636,6 +4834,11 @@ static hipError_t scan_pod_f(const DevTable &t, const void *pods_, const DPodX *
     // the column-major copy exists for compact-layout tables only
     constexpr bool kSoaOk = (F & (kFeatNorm | kFeatWide)) == 0;
     const bool soa = kSoaOk && t.soa.c[0];
+    // part & 128 (kFeatAA classes): pod s is a soft-spread pod (spec S14).  It runs the pre-pass in the
+    // classes without a normalizing plugin too, and on a table that keeps the column-major copy it
+    // goes through the row kernels (which stride over any grid) with the grid of the column scan, so
+    // the commit reduces the partials it reduces for every other pod.
+    const bool softp = (F & kFeatAA) != 0 && (part & 128) != 0;
     // one partial key per block; a grid of <= 2048 blocks (8 four-wave blocks per CU) strides
     const uint32_t units = soa ? (t.n + 3) / 4 : t.n;
     uint32_t blocks = min(kScanBlocksMax, max(1u, (units + 255) / 256));
@@ -4655,12 +4858,13 @@ static hipError_t scan_pod_f(const DevTable &t, const void *pods_, const DPodX *
                     return (uint32_t)std::max(1, std::min((int)kScanBlocksMax, cus * per));
                 }();
                 blocks = min(blocks, min(kScanBlocksMax, resident));
-                hipLaunchKernelGGL((k_scan_soa<F>), dim3(blocks), dim3(256), 0, stream, t, pods, s, c, sc,
-                                   feas, score, total);
+                if (!softp)
+                    hipLaunchKernelGGL((k_scan_soa<F>), dim3(blocks), dim3(256), 0, stream, t, pods, s, c, sc,
+                                       feas, score, total);
             }
         }
-        if (!soa) {
-            if (F & kFeatNorm)
+        if (!soa || softp) {
+            if ((F & kFeatNorm) || softp)
                 hipLaunchKernelGGL((k_scan_norm<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx, s, sc);
             hipLaunchKernelGGL((k_scan_key<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx, s, c, sc,
                                feas, score, total);
@@ -4696,12 +4900,22 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
     if ((F & kFeatNorm) && podx) px = *podx;
     if (gs && t.n > 0) {
         const uint32_t g = (t.n + kScorePodGT - 1) / kScorePodGT;
-        if constexpr ((F & kFeatNorm) != 0)
+        if constexpr ((F & kFeatNorm) != 0) {
             hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, p, px, gs, pidx,
                                prow);
+        } else if constexpr ((F & kFeatAA) != 0) {
+            // a soft-spread pod (spec S14) needs the pre-pass for its feasible-zones word
+            if (pod_soft(p.flags))
+                hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, p, px, gs, pidx,
+                                   prow);
+        }
         hipLaunchKernelGGL((k_score_podg<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, p, px, c, hout, gs, seq,
                            pidx, prow);
         return hipGetLastError();
+    }
+    if constexpr ((F & kFeatAA) != 0) {
+        // the single-workgroup form carries no zone scores (the host always passes the device words)
+        if (pod_soft(p.flags)) return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL((k_score_pod1<F>), dim3(1), dim3(1024), 0, stream, t, p, px, c, hout, seq, pidx, prow);
     return hipGetLastError();

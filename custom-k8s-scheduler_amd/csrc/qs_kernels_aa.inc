@@ -39,12 +39,20 @@ __global__ void k_aa_apply(DevTable t, uint32_t node, uint32_t app, int32_t sign
 hipError_t QS_AA_FN(persistent)(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                 const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st, hipStream_t stream) {
     if (!t.apps) return hipErrorInvalidValue;
+    if (c.feat & kFeatSoft) {  // the stream holds soft-spread pods (spec S14)
+        if (c.feat & kFeatNorm) return persistent_f<kAN, true>(t, pods, podx, P, c, on, ok, st, stream);
+        if (c.feat & kFeatRes) return persistent_f<kAG, true>(t, pods, podx, P, c, on, ok, st, stream);
+        return persistent_f<kAD, true>(t, pods, podx, P, c, on, ok, st, stream);
+    }
     if (c.feat & kFeatNorm) return persistent_f<kAN>(t, pods, podx, P, c, on, ok, st, stream);
     if (c.feat & kFeatRes) return persistent_f<kAG>(t, pods, podx, P, c, on, ok, st, stream);
     return persistent_f<kAD>(t, pods, podx, P, c, on, ok, st, stream);
 }
 
 uint32_t QS_AA_FN(persistent_max_nodes)(uint32_t feat) {
+    if (feat & kFeatSoft)
+        return (feat & kFeatNorm) ? persistent_cap<kAN, true>()
+                                  : (feat & kFeatRes) ? persistent_cap<kAG, true>() : persistent_cap<kAD, true>();
     return (feat & kFeatNorm) ? persistent_cap<kAN>() : (feat & kFeatRes) ? persistent_cap<kAG>() : persistent_cap<kAD>();
 }
 

@@ -49,7 +49,9 @@ uint32_t persistent_max_nodes(uint32_t feat);
 hipError_t launch_scan_pod(const DevTable &t, const void *pods, const DPodX *podx, uint32_t s,
                            const DevCfg &c, void *scratch, int32_t *out_node, uint64_t *out_key,
                            uint64_t *stamps, uint8_t *feas, int32_t *score, int32_t *total,
-                           int part, hipStream_t stream);  // part: 1 keys (+norm), 2 commit
+                           int part, hipStream_t stream);  // part: 1 keys (+norm), 2 commit; | 128 on both calls
+                                                           // of a soft-spread pod (spec S14, kFeatAA classes:
+                                                           // the pre-pass in every class, the row kernels)
 hipError_t launch_rows_to_soa(const DevTable &t, hipStream_t stream);
 // qs_score_pod in ONE launch (two for NormalizeScore profiles): pod record (DPod / DPodW) and
 // extension by value; outputs written into pinned host memory hout (score_pod1_pack_bytes(n) bytes:

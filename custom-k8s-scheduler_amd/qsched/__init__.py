@@ -26,11 +26,11 @@ from ._abi import (ENGINES, ENGINE_NAMES, EXPORTED, LIB_PATH, POD_DTYPE, QS_ABI_
 __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_struct", "fit_error_message",
            "synth_generate", "shape_table", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
            "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH",
-           "aa_spread", "aa_kind", "aa_max_skew", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
+           "aa_spread", "aa_spread_soft", "aa_is_soft", "aa_kind", "aa_max_skew", "QS_AA_SOFT", "QS_MAX_ZONES", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
            "QS_MAX_SPREAD_SKEW"]
 
-from ._abi import (QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
-                   QS_MAX_SPREAD_SKEW)
+from ._abi import (QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
+                   QS_MAX_SPREAD_SKEW, QS_MAX_ZONES)
 
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
 
@@ -41,6 +41,18 @@ def aa_spread(max_skew: int) -> int:
     if not 1 <= int(max_skew) <= QS_MAX_SPREAD_SKEW:
         raise ValueError("max_skew must be 1..31")
     return QS_AA_SPREAD_ZONE | (int(max_skew) << 8)
+
+
+def aa_spread_soft(max_skew: int) -> int:
+    """QS_AA_SPREAD_SOFT(max_skew): the same constraint with ``whenUnsatisfiable: ScheduleAnyway`` (spec
+    S14): the pod is not filtered by spread; every feasible node's total gains the PodTopologySpread
+    score of its zone times ``Scheduler.set_topology_spread_weight``."""
+    return aa_spread(max_skew) | QS_AA_SOFT
+
+
+def aa_is_soft(anti_affinity):
+    """QS_AA_IS_SOFT: the ScheduleAnyway flag (scalar or array)."""
+    return (anti_affinity >> 16) & 1
 
 
 def aa_kind(anti_affinity):
@@ -221,6 +233,23 @@ class Scheduler:
         self._chk(self.lib.qs_get_pod_anti_affinity(self.ctx, ctypes.byref(on)))
         return bool(on.value)
 
+    def set_topology_spread_weight(self, weight: int):
+        """qs_set_topology_spread_weight: the PodTopologySpread plugin weight of QS_AA_SPREAD_SOFT pods
+        (spec S14), 0..100; 2 in a new context."""
+        self._chk(self.lib.qs_set_topology_spread_weight(self.ctx, int(weight)))
+
+    def get_topology_spread_weight(self) -> int:
+        w = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_topology_spread_weight(self.ctx, ctypes.byref(w)))
+        return int(w.value)
+
+    def score_pod_zone_scores(self):
+        """qs_score_pod_zone_scores: int32[QS_MAX_ZONES], the PodTopologySpread score per zone of the last
+        score_pod / score_pod_packed call (-1: no feasible node there, or no soft-spread pod)."""
+        z = np.full(QS_MAX_ZONES, -2, np.int32)
+        self._chk(self.lib.qs_score_pod_zone_scores(self.ctx, _ptr(z)))
+        return z
+
     def mailbox_export(self) -> bytes:
         """qs_dist_mailbox_export: this rank's 64-byte mailbox IPC handle (sharded contexts opened
         without an RCCL id)."""
@@ -299,7 +328,7 @@ class Scheduler:
     # ---- one pod, all nodes ----
     def score_pod(self, pod, outputs=True, out=None):
         """qs_score_pod: {"best"} and, with outputs, the per-node "feasible" / "scores" / "total"
-        arrays (fresh copies, or the caller's reusable buffers from score_buffers() passed as
+        arrays and the per-zone "zone_scores" of a soft-spread pod (fresh copies, or the caller's reusable buffers from score_buffers() passed as
         `out`, filled in place).  outputs=False asks the library for the best node only."""
         p = np.array([pod], POD_DTYPE) if isinstance(pod, np.void) else pods_to_struct(pod)[:1]
         best = ctypes.c_int32(-2)
@@ -313,7 +342,10 @@ class Scheduler:
             raise ValueError("score_pod: out buffers do not match the node table (use score_buffers())")
         self._chk(self.lib.qs_score_pod(self.ctx, _ptr(p), _ptr(feas), _ptr(score), _ptr(total),
                                         ctypes.byref(best)))
-        return dict(feasible=feas, scores=score, total=total, best=best.value)
+        # the fifth score per zone (spec S14): one more call, for a soft-spread pod only; all -1 otherwise
+        soft = aa_is_soft(int(p["anti_affinity"][0]))
+        zs = self.score_pod_zone_scores() if soft else np.full(QS_MAX_ZONES, -1, np.int32)
+        return dict(feasible=feas, scores=score, total=total, best=best.value, zone_scores=zs)
 
     def score_pod_packed(self, pod):
         """qs_score_pod_packed: (best, packed) with packed a copy of the n per-node words (0xFFFFFFFF

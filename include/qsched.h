@@ -79,7 +79,12 @@ typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
  * more than max_skew pods of the app above the emptiest zone that holds a node of the table.  The kind
  * sits in the low byte of qs_pod.anti_affinity and max_skew (1..31) in bits 8-12: QS_AA_SPREAD(max_skew).
  * Upper bits must be zero for the other kinds; a pod has one kind.  Honoured like the other kinds on a
- * context that tracks; QS_MODE_BATCHED refuses a stream that holds such a pod (QS_EINVAL). */
+ * context that tracks; QS_MODE_BATCHED refuses a stream that holds such a pod (QS_EINVAL).
+ * QS_AA_SPREAD_SOFT(max_skew) (spec S14) is the same constraint with whenUnsatisfiable: ScheduleAnyway
+ * (UP plugins/podtopologyspread Score / NormalizeScore): kind 3 with the flag QS_AA_SOFT above max_skew.
+ * Such a pod is not filtered by spread; on a context that tracks, every feasible node's total gains
+ * Wpts * PTS(zone of the node), PTS in 0..100 from the app's recorded pods per zone over the zones that
+ * hold a node feasible for the pod (qs_set_topology_spread_weight; qs_score_pod_zone_scores). */
 typedef enum qs_anti_affinity {
     QS_AA_NONE = 0, QS_AA_HOSTNAME = 1, QS_AA_ZONE = 2, QS_AA_SPREAD_ZONE = 3
 } qs_anti_affinity;
@@ -87,6 +92,9 @@ typedef enum qs_anti_affinity {
 #define QS_AA_KIND(x) ((int32_t)((x) & 0xFF))
 #define QS_AA_MAX_SKEW(x) ((int32_t)(((x) >> 8) & 0x1F))
 #define QS_MAX_SPREAD_SKEW 31
+#define QS_AA_SOFT ((int32_t)0x10000) /* only with QS_AA_SPREAD_ZONE: ScheduleAnyway (spec S14) */
+#define QS_AA_SPREAD_SOFT(max_skew) ((int32_t)(QS_AA_SPREAD(max_skew) | QS_AA_SOFT))
+#define QS_AA_IS_SOFT(x) ((int32_t)(((x) >> 16) & 1))
 
 /* Scoring resources (spec/semantics.md S5 "Scoring resources"): cpu, memory, or one of the table's
  * two extended-resource columns (the caller interns e.g. "amd.com/gpu" as QS_RES_EXT0). */
@@ -322,6 +330,12 @@ QS_API qs_status qs_get_scoring_strategy_qos(qs_ctx *ctx, int32_t qos, qs_scorin
  * output pointer. */
 QS_API qs_status qs_set_pod_anti_affinity(qs_ctx *ctx, int32_t on);
 QS_API qs_status qs_get_pod_anti_affinity(qs_ctx *ctx, int32_t *on);
+/* Weight of the PodTopologySpread score (spec S14: Wpts, UP apis/config/v1/default_plugins.go weight 2)
+ * of the context, 0..100, 2 in a new context.  Only QS_AA_SPREAD_SOFT pods on a context that tracks pod
+ * anti-affinity get the term.  QS_ESTATE while the context holds prepared streams; QS_EINVAL outside
+ * 0..100 and for null pointers. */
+QS_API qs_status qs_set_topology_spread_weight(qs_ctx *ctx, int32_t w);
+QS_API qs_status qs_get_topology_spread_weight(qs_ctx *ctx, int32_t *w);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);
@@ -355,6 +369,12 @@ QS_API qs_status qs_score_pod(qs_ctx *ctx, const qs_pod *pod, uint8_t *feasible_
  * The words are what the kernel wrote into pinned host memory, so a plugin's per-node Filter / Score
  * lookups read them in place (UP framework/interface.go#ScorePlugin.Score is called per node). */
 QS_API qs_status qs_score_pod_packed(qs_ctx *ctx, const qs_pod *pod, const uint32_t **packed_n, int32_t *best);
+/* The fifth plugin score of the last qs_score_pod / qs_score_pod_packed call on ctx, per zone (spec S14):
+ * out[z] = PTS of every node of zone z (0..100) for the zones that hold a node feasible for that pod, -1
+ * for every other zone; all -1 when that pod was no QS_AA_SPREAD_SOFT pod or the context does not track.
+ * score_n[n][4] and the packed words keep their four scores: a framework plugin looks this one up by the
+ * node's zone.  total_n and best of that call include Wpts * PTS.  QS_ESTATE before any such call. */
+QS_API qs_status qs_score_pod_zone_scores(qs_ctx *ctx, int32_t out[QS_MAX_ZONES]);
 
 /* ---- exact stream ---- */
 QS_API qs_status qs_schedule_stream(qs_ctx *ctx, const qs_pod *pods, uint32_t p, qs_mode mode,

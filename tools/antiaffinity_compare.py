@@ -10,6 +10,8 @@ Arms per table:
   aa_scan           tracking on, QS_ENGINE_SCAN
   spread_persistent the aa_* arms with the ZONE apps' pods turned into SPREAD(1) (zone topology spread, spec S13,
   spread_scan       DESIGN.md §3.5), checked against tests/spread_ref.py; read beside aa_* of the same run
+  soft_persistent   the spread_* arms with the SPREAD(1) pods turned soft (zone topology spread scoring, spec S14,
+  soft_scan         DESIGN.md §3.6), checked against tests/soft_spread_ref.py; read beside spread_* of the same run
   plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
   plain_scan        the cost of the filter and the recording is aa_* against plain_*
 
@@ -27,7 +29,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "plain_persistent", "plain_scan"]
+ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "soft_persistent", "soft_scan",
+        "plain_persistent", "plain_scan"]
 
 
 def paths(tree):
@@ -45,13 +48,19 @@ def run_arm(n, p, arm, steps, prefix):
 
     nodes, pods = synth_generate(5, n, p)
     nodes, pods = A.fold(nodes, pods, 40, 4)
-    spread = arm.startswith("spread_")
+    soft = arm.startswith("soft_")
+    spread = arm.startswith("spread_") or soft
     tracked = arm.startswith("aa_") or spread
     if spread:
         import spread_ref as S
 
         pods = pods.copy()
-        pods["anti_affinity"][pods["anti_affinity"] == A.ZONE] = S.spread(1)
+        kind = S.spread(1)
+        if soft:
+            import soft_spread_ref as R
+
+            kind = R.spread_soft(1)
+        pods["anti_affinity"][pods["anti_affinity"] == A.ZONE] = kind
     batched = arm == "batched1"
     engine = "auto" if batched else arm.split("_")[1]
     cfg = dict(engine=engine, batch_pods=1) if batched else dict(engine=engine)
@@ -75,7 +84,9 @@ def run_arm(n, p, arm, steps, prefix):
             return out
         pl, keys = head.results()
         head.free()
-        if spread:
+        if soft:
+            ref = R.run(nodes, pods[:prefix])
+        elif spread:
             ref = S.run(nodes, pods[:prefix])
         elif tracked or batched:
             ref = A.run(nodes, pods[:prefix])
