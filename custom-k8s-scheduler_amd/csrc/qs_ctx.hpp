@@ -151,6 +151,14 @@ struct qs_stream {
     // per stream position (after the QoS sort): 1 = a QS_AA_SPREAD_SOFT pod (spec S14); the SCAN launch
     // sequence gives such a pod the pre-pass in every class
     std::vector<uint8_t> soft;
+    // ... 1 = a QS_AA_SPREAD_HOSTNAME pod (spec S15), and their number.  These pods take no slot of
+    // spread_row: their counts are per node, not per zone.
+    std::vector<uint8_t> hosts;
+    uint32_t host_pods = 0;
+    // ... and their distinct apps as the quarter row k_persistent reads (slot j -> app, -1 = unused; the
+    // first kHostSpreadApps of them) with their number (above kHostSpreadApps the stream runs SCAN)
+    int32_t host_row[16];
+    uint32_t host_apps = 0;
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
     // Uniform windows: run0[k] = first stream position of the run of byte-identical
@@ -195,6 +203,13 @@ struct qs_ctx {
     int32_t w_pts = 2;  // PodTopologySpread plugin weight (qs_set_topology_spread_weight, spec S14; upstream's default)
     int32_t score_zs[qs::kMaxZones];  // the zone scores of the last qs_score_pod call (qs_score_pod_zone_scores)
     bool score_zs_valid = false;
+    // Hostname topology spread (spec S15): uint16 pods per (app, node), [kMaxApps][cap],
+    // allocated when the context first meets such a pod (nullptr: never, and nothing is kept).  The
+    // mirror (aa_node) is authoritative; hc_valid says that the array equals it.  k_aa_apply and the
+    // kFeatAA k_scan_commit keep it valid, every other writer of recorded pods clears the flag, and the
+    // array is rebuilt from the mirror before the next launch that reads it.
+    qs_host::DevBuf hcount, hc_idx, hc_val;
+    bool hc_valid = false;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

@@ -68,6 +68,10 @@ constexpr uint32_t kMaxApps = 1024, kMaxZones = 64, kAppWords = kMaxApps / 32;
 // PodTopologySpread plugin weight Wpts (word 0 of row kMaxApps + 4).
 constexpr uint32_t kSpreadRows = 5, kSpreadApps = 64;
 static_assert(kSpreadApps <= kMaxZones, "the spread apps fill one row");
+// Hostname topology spread (spec S15) uses free words of the weight's row (kMaxApps + 4): words 2-3 the
+// address of the uint16 (app, node) counts (null: the context keeps none), words 16-31 the hostname-spread
+// apps of a PERSISTENT stream (kHostSpreadApps entries, -1 = unused; the LDS slots of k_persistent<..., HOST>).
+constexpr uint32_t kHostSpreadApps = 16;
 struct DevTable {
     DRow *rows;       // compact layout (nullptr in the wide layout)
     DRowW *wrows;     // wide layout (nullptr in the compact layout)
@@ -94,9 +98,10 @@ struct DevTable {
 // anti-affinity (qs_set_pod_anti_affinity); its instantiations live in qs_kernels_aa.inc.
 // kFeatSoft (with kFeatAA) says that the stream holds soft-spread pods (spec S14).  No kernel is a
 // template over it: the host's dispatch picks the k_persistent instantiations that carry the score, and
-// their node caps, by it.
+// their node caps, by it.  kFeatHost likewise: the stream holds hostname-spread pods (spec S15), and
+// PERSISTENT runs the instantiations that keep the (app, node) counts in LDS.
 enum FeatBits : uint32_t { kFeatTaint = 1u, kFeatAffinity = 2u, kFeatExt = 4u, kFeatWide = 8u, kFeatRes = 16u,
-                           kFeatStrat = 32u, kFeatAA = 64u, kFeatSoft = 128u };
+                           kFeatStrat = 32u, kFeatAA = 64u, kFeatSoft = 128u, kFeatHost = 256u };
 
 // pod flags: bits 0-1 QoS, 2-3 the NodeResourcesFit strategy of the pod's QoS class (0 Least, 1 Most,
 // 2 RequestedToCapacityRatio; read by the kFeatStrat scorer only, every other reader masks its own

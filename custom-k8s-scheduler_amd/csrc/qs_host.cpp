@@ -350,6 +350,13 @@ void fill_spread_cfg(const qs_ctx *c, int32_t *rows) {
     std::memset(rows, 0, 3 * kMaxZones * 4);
     std::memcpy(rows, kLogTab, sizeof kLogTab);
     rows[2 * kMaxZones] = c->w_pts;
+    // words 2-3 of the weight's row: the address of the (app, node) counts of spec S15, null while the
+    // context keeps none (aa_hcount in qs_kernels.hpp reads it)
+    const uint64_t hp = (uint64_t)(uintptr_t)c->hcount.p;
+    std::memcpy(rows + 2 * kMaxZones + 2, &hp, 8);
+    // words 16-31: the hostname-spread apps of the PERSISTENT stream in flight (none: a stream writes its own)
+    static_assert(kHostSpreadApps == 16, "one quarter row");
+    for (uint32_t j = 0; j < kHostSpreadApps; j++) rows[2 * kMaxZones + 16 + j] = -1;
 }
 // ... written alone by qs_set_topology_spread_weight and after qs_table_restore (whose snapshot holds
 // the weight of its save); every table upload writes them with the domain flags (write_domains).
@@ -377,6 +384,65 @@ void write_domains(qs_ctx *c) {
     HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)kMaxApps * kMaxZones, rows, sizeof rows, hipMemcpyHostToDevice,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // (rows lives on this stack)
+}
+
+// Hostname topology spread (spec S15): the device's uint16 pods per (app, node), 2 KB per node.
+constexpr uint32_t kHcMaxNodes = 1u << 19;  // 1 GiB
+constexpr int64_t kHcMaxPods = 65535;
+// The sparse mirror map as the dense array's non-zero cells (no HIP call): cell app * cap + node.
+void hc_cells(const Mirror &m, uint32_t cap, std::vector<uint32_t> &idx, std::vector<uint16_t> &val) {
+    idx.clear();
+    val.clear();
+    for (const auto &e : m.aa_node) {
+        const uint32_t app = (uint32_t)(e.first >> 32), node = (uint32_t)e.first;
+        if (app >= kMaxApps || node >= m.n || node >= cap || e.second <= 0) continue;
+        idx.push_back(app * cap + node);
+        val.push_back((uint16_t)std::min<int64_t>(e.second, kHcMaxPods));
+    }
+}
+// A table upload (load, re-layout, append, rebuild after a fault): the array follows the table's
+// capacity and is stale; a table it cannot cover drops it (the next such pod is refused).
+void hc_on_upload(qs_ctx *c) {
+    c->hc_valid = false;
+    if (!c->hcount.p) return;
+    if (!c->dt.apps || c->cap > kHcMaxNodes) {
+        (void)hipFree(c->hcount.p);
+        c->hcount.p = nullptr;
+        c->hcount.bytes = 0;
+        return;
+    }
+    c->hcount.ensure((size_t)kMaxApps * c->cap * 2);
+}
+// Before every launch that reads the counts: allocate on first use, rebuild from the mirror when stale.
+void ensure_hcount(qs_ctx *c) {
+    aa_check_table(c);
+    if (c->hcount.p && c->hc_valid) return;
+    if (c->cap > kHcMaxNodes)
+        fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME keeps 2 KB of counts per node: tables up to 2^19 nodes");
+    for (uint32_t i = 0; i < c->m.n; i++)
+        if (c->m.mp[i] > kHcMaxPods)
+            fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME counts pods per node in 16 bits: node " + std::to_string(i) +
+                                " has max_pods above 65535");
+    const size_t cells = (size_t)kMaxApps * c->cap;
+    const void *before = c->hcount.p;
+    c->hcount.ensure(cells * 2);
+    HIPCHK(hipMemsetAsync(c->hcount.p, 0, cells * 2, c->stream));
+    std::vector<uint32_t> idx;
+    std::vector<uint16_t> val;
+    hc_cells(c->m, c->cap, idx, val);
+    if (!idx.empty()) {
+        const uint32_t m = (uint32_t)idx.size();
+        c->hc_idx.ensure((size_t)m * 4);
+        c->hc_val.ensure((size_t)m * 2);
+        HIPCHK(hipMemcpyAsync(c->hc_idx.p, idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->hc_val.p, val.data(), (size_t)m * 2, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_hc_scatter, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->hcount.as<uint16_t>(),
+                           c->hc_idx.as<uint32_t>(), c->hc_val.as<uint16_t>(), m, (uint32_t)cells);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));  // (idx / val live on this stack)
+    if (c->hcount.p != before) write_spread_cfg(c);  // the kernels find the array through the weight's row
+    c->hc_valid = true;
 }
 
 // Upload the whole mirror to the device in the context's layout (c->wide, c->shift).
@@ -416,6 +482,7 @@ void upload_table(qs_ctx *c) {
     // a (re)loaded table starts with no pods recorded; what the mirror of a context that tracks pod
     // anti-affinity holds (spec S12) is rebuilt: a re-layout, or the recovery after a device fault
     std::vector<uint32_t> aw;
+    hc_on_upload(c);  // (before write_domains, whose rows carry the array's address)
     if (c->dt.apps) {
         const bool rebuild = !c->m.aa_node.empty();
         if (rebuild) {
@@ -525,16 +592,23 @@ void check_pod(const qs_pod &p, uint32_t j) {
     const int32_t kind = QS_AA_KIND(p.anti_affinity);
     if (p.anti_affinity < 0 || kind > QS_AA_SPREAD_ZONE) bad("anti_affinity kind must be 0..3");
     if (kind == QS_AA_SPREAD_ZONE) {
-        // ... and QS_AA_SOFT above it (spec S14), the only bit above max_skew
-        const int32_t skew = (p.anti_affinity & ~QS_AA_SOFT) >> 8;
+        // ... and QS_AA_SOFT (spec S14) or QS_AA_HOSTKEY (spec S15) above it, the only bits above max_skew
+        const int32_t skew = (p.anti_affinity & ~(QS_AA_SOFT | QS_AA_HOSTKEY)) >> 8;
         if (skew < 1 || skew > QS_MAX_SPREAD_SKEW) bad("anti_affinity: max_skew of QS_AA_SPREAD must be 1..31");
+        if (QS_AA_IS_SOFT(p.anti_affinity) && QS_AA_IS_HOSTKEY(p.anti_affinity))
+            bad("anti_affinity: QS_AA_SOFT and QS_AA_HOSTKEY exclude each other (no ScheduleAnyway form of the "
+                "hostname spread)");
     } else if (p.anti_affinity != kind) {
-        bad("anti_affinity: bits above the kind must be zero (only QS_AA_SPREAD carries max_skew and QS_AA_SOFT)");
+        bad("anti_affinity: bits above the kind must be zero (only QS_AA_SPREAD carries max_skew, QS_AA_SOFT and "
+            "QS_AA_HOSTKEY)");
     }
 }
 // (a soft-spread pod too, spec S14: k_persistent needs its app's counts like a SPREAD pod's)
 bool pod_spreads(const qs_pod &p) { return QS_AA_KIND(p.anti_affinity) == QS_AA_SPREAD_ZONE; }
 bool pod_soft_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_SOFT(p.anti_affinity); }
+// (spec S15: kind 3 on the host, so pod_spreads() holds and batched mode refuses it; its counts are per
+// node, so it takes no slot among the zone-spread apps)
+bool pod_host_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_HOSTKEY(p.anti_affinity); }
 
 // NodeAffinity disabled (config.enable_affinity = 0): the pod's required / preferred term counts are
 // recorded as 0, so the normalizing kernels (which evaluate both plugins) neither filter nor score
@@ -542,13 +616,16 @@ bool pod_soft_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_SOFT(p
 // the kFeatStrat scorer reads (check_pod has bounded qos to 0..2).  Bits 12-13: the anti-affinity kind;
 // bits 26-30: max_skew of a QS_AA_SPREAD pod (0 for every other kind; spec S13, read by the kFeatAA
 // kernels only).  Bit 31 stays the batched claim's.  A QS_AA_SPREAD_SOFT pod (spec S14) carries kind 0,
-// so that no filter knows it, bit 14, and its max_skew.
+// so that no filter knows it, bit 14, and its max_skew; a QS_AA_SPREAD_HOSTNAME pod (spec S15) likewise
+// kind 0, bit 15, and its max_skew.  Bits 7 and 11 stay free in the record (the score path's launcher
+// uses bit 7 of its own copy).
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
-    const bool soft = pod_soft_spread(p);
+    const bool soft = pod_soft_spread(p), host = pod_host_spread(p);
     return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
-           (aff * (uint32_t)p.n_pref_terms << 8) | ((soft ? 0u : (uint32_t)QS_AA_KIND(p.anti_affinity)) << 12) |
-           ((soft ? 1u : 0u) << 14) | ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
+           (aff * (uint32_t)p.n_pref_terms << 8) |
+           ((soft || host ? 0u : (uint32_t)QS_AA_KIND(p.anti_affinity)) << 12) | ((soft ? 1u : 0u) << 14) |
+           ((host ? 1u : 0u) << 15) | ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
 }
 
 // Device pod record in the context's layout: DPod (compact, memory in 2^shift units) or DPodW
@@ -801,7 +878,7 @@ struct KernelTimer {
 uint32_t la_window(const qs_ctx *c);
 bool la_overlap(const qs_ctx *c);
 
-int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false) {
+int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host_over = false) {
     int e = c->cfg.engine;
     const uint32_t feat = c->dc.feat;
     if (feat & kFeatAA) {
@@ -815,8 +892,15 @@ int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false) {
         if (spread_over && e == QS_ENGINE_PERSISTENT)
             fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD / QS_AA_SPREAD_SOFT pods of at most " + std::to_string(kSpreadApps) +
                                 " distinct apps per stream");
+        // hostname topology spread (spec S15): the persistent workgroup keeps the (app, node) counts of at
+        // most kHostSpreadApps apps in LDS, and has no instantiation with the soft-spread score as well
+        if (host_over && e == QS_ENGINE_PERSISTENT)
+            fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD_HOSTNAME pods of at most " +
+                                std::to_string(kHostSpreadApps) + " distinct apps per stream, and not together "
+                                "with QS_AA_SPREAD_SOFT pods");
         if (e == QS_ENGINE_AUTO)
-            e = n <= persistent_max_nodes(feat) && !spread_over ? QS_ENGINE_PERSISTENT : QS_ENGINE_SCAN;
+            e = n <= persistent_max_nodes(feat) && !spread_over && !host_over ? QS_ENGINE_PERSISTENT
+                                                                               : QS_ENGINE_SCAN;
     }
     if (e == QS_ENGINE_AUTO) {
         if (n > 0 && la_geometry(n, la_window(c), shard_plan(c).W, 2 * la_window(c)).G > 0)
@@ -1291,6 +1375,9 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         one.zone[0] = r->zone;
         one.gen[0] = generation;
         check_row_values(one, 0);
+        if (c->hcount.p && r->max_pods > kHcMaxPods)
+            fail(QS_EINVAL, "max_pods above 65535 on a context that counts pods per (app, node) in 16 bits "
+                            "(QS_AA_SPREAD_HOSTNAME, spec S15)");
         if (c->aa_track && idx < m.n && r->zone != m.zone[idx] && m.aa_holds(idx))
             fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
                             "cannot change while tracking is on");
@@ -1348,6 +1435,9 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
             if (sign < 0 && c->m.aa_count(app, node) == 0)
                 fail(QS_EINVAL, "qs_unreserve: no pod of app " + std::to_string(app) + " is recorded on node " +
                                     std::to_string(node));
+            // a hostname-spread pod (spec S15): the context keeps the (app, node) counts from here on
+            // (k_aa_apply below maintains them)
+            if (pod_host_spread(*p) && c->dev_valid) ensure_hcount(c);
         }
         sync_mirror(c);
         const RowSnap before = snap_row(c->m, node);
@@ -1610,6 +1700,8 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
         c->score_zs_valid = true;
         return nullptr;
     }
+    // a hostname-spread pod (spec S15) reads the (app, node) counts: allocated / rebuilt first
+    if (c->aa_track && pod_host_spread(*pod)) ensure_hcount(c);
     const DPodX dx = compact_podx(c, *pod);
     // (behind the packed words: the 64 zone scores of a soft-spread pod, spec S14)
     const size_t pb = score_pod1_pack_bytes(n) + kMaxZones * 4;
@@ -1623,7 +1715,7 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
         std::memset(c->pin, 0, pb);
     }
     if (!c->score_gs.p) {
-        c->score_gs.ensure(64);  // (+ the feasible-zones word of a soft-spread pod)
+        c->score_gs.ensure(64);  // (+ the feasible-zones word of a soft-spread pod, the minimum of a hostname-spread pod)
         HIPCHK(hipMemsetAsync(c->score_gs.p, 0, 64, c->stream));
     }
     const uint32_t pidx = c->pend < n ? c->pend : 0xFFFFFFFFu;
@@ -1710,7 +1802,8 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
             std::vector<uint8_t> seen(kMaxApps, 0);
             std::fill(std::begin(s->spread_row), std::end(s->spread_row), -1);
             for (uint32_t j = 0; j < p; j++) {
-                if (!pod_spreads(pods[j]) || seen[(uint32_t)pods[j].app]) continue;
+                // (a hostname-spread pod, spec S15, needs no zone counts and takes no slot)
+                if (!pod_spreads(pods[j]) || pod_host_spread(pods[j]) || seen[(uint32_t)pods[j].app]) continue;
                 seen[(uint32_t)pods[j].app] = 1;
                 if (s->spread_apps < kSpreadApps) s->spread_row[s->spread_apps] = pods[j].app;
                 ++s->spread_apps;
@@ -1721,9 +1814,21 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         const bool needx = feat_of(c->cfg) & (kFeatTaint | kFeatAffinity);
         std::vector<DPodX> dx(needx ? std::max<uint32_t>(p, 1) : 1);
         s->soft.assign(p, 0);
+        s->hosts.assign(p, 0);
+        s->host_pods = 0;
+        s->host_apps = 0;
+        std::fill(std::begin(s->host_row), std::end(s->host_row), -1);
+        std::vector<uint8_t> host_seen(kMaxApps, 0);
         for (uint32_t k = 0; k < p; k++) {
             const uint32_t j = s->order[k];
             s->soft[k] = pod_soft_spread(pods[j]) ? 1 : 0;
+            s->hosts[k] = pod_host_spread(pods[j]) ? 1 : 0;
+            s->host_pods += s->hosts[k];
+            if (s->hosts[k] && !host_seen[(uint32_t)pods[j].app]) {  // the distinct apps, for k_persistent's slots
+                host_seen[(uint32_t)pods[j].app] = 1;
+                if (s->host_apps < kHostSpreadApps) s->host_row[s->host_apps] = pods[j].app;
+                ++s->host_apps;
+            }
             compact_pod(c, pods[j], j, c->shift, c->wide, dp.data() + rb * k);
             if (needx) dx[k] = compact_podx(c, pods[j]);
         }
@@ -1757,8 +1862,8 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         if (!s) fail(QS_EINVAL, "null stream");
         if (mode != QS_MODE_EXACT && mode != QS_MODE_BATCHED) fail(QS_EINVAL, "unknown qs_mode");
         if (s->shift != c->shift || s->wide != c->wide) fail(QS_ESTATE, "node table re-laid out after prepare");
-        if (mode == QS_MODE_BATCHED && s->spread_apps != 0)
-            fail(QS_EINVAL, "QS_MODE_BATCHED does not know zone topology spread (QS_AA_SPREAD / QS_AA_SPREAD_SOFT pods, spec S13, S14): "
+        if (mode == QS_MODE_BATCHED && (s->spread_apps != 0 || s->host_pods != 0))
+            fail(QS_EINVAL, "QS_MODE_BATCHED does not know topology spread (QS_AA_SPREAD / QS_AA_SPREAD_SOFT / QS_AA_SPREAD_HOSTNAME pods, spec S13-S15): "
                             "run the stream in QS_MODE_EXACT on a context that tracks pod anti-affinity");
         HIPCHK(hipSetDevice(c->device));
         // from here on the device table (and d_node) may change even if this run fails part way
@@ -1783,7 +1888,22 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         }
         // zone topology spread (spec S13): k_persistent keeps the counts of at most kSpreadApps apps
         const bool spread_over = aa_exact && s->spread_apps > kSpreadApps;
-        const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n, spread_over);
+        // hostname topology spread (spec S15): the k_persistent instantiations that keep the (app, node)
+        // counts of the stream's hostname-spread apps in LDS (kFeatHost), for at most kHostSpreadApps apps
+        // and no soft pod in the same stream
+        const bool host_spread = aa_exact && s->host_pods != 0;
+        const bool has_soft = aa_exact && (c->dc.feat & kFeatSoft) != 0;
+        const bool host_over = host_spread && (s->host_apps > kHostSpreadApps || has_soft);
+        if (host_spread && !host_over) c->dc.feat |= kFeatHost;
+        const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n, spread_over, host_over);
+        // the (app, node) counts: brought up to date for a stream that reads them; kept by the tracked
+        // SCAN commit alone, so every other run that records pods on a tracking context leaves them stale
+        // (k_persistent loads them at entry and keeps its own in LDS)
+        if (host_spread && n > 0) ensure_hcount(c);
+        if (c->aa_track && !(aa_exact && eng == QS_ENGINE_SCAN)) c->hc_valid = false;
+        if (host_spread && eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
+            HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 4) * kMaxZones + 16, s->host_row,
+                                  sizeof s->host_row, hipMemcpyHostToDevice, c->stream));
         if (aa_exact && eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
             HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 1) * kMaxZones, s->spread_row,
                                   sizeof s->spread_row, hipMemcpyHostToDevice, c->stream));
@@ -1815,7 +1935,8 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
                 ensure_soa(c);
                 for (uint32_t k = 0; k < P; k++) {
                     // (128: a soft-spread pod of a tracked stream, spec S14: the pre-pass in every class)
-                    const int sp = aa_exact && s->soft[k] ? 128 : 0;
+                    // (256: a hostname-spread pod, spec S15: the pre-pass for the minimum of its app's counts)
+                    const int sp = !aa_exact ? 0 : s->soft[k] ? 128 : s->hosts[k] ? 256 : 0;
                     kt.begin(1, c->stream);  // the key scan alone (+ normalize pre-pass)
                     HIPCHK(launch_scan_pod(c->dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st,
                                            nullptr, nullptr, nullptr, 1 | sp, c->stream));
@@ -2446,7 +2567,9 @@ qs_status qs_table_restore(qs_ctx *c) {
             fail(QS_ESTATE, "no matching qs_table_save snapshot");
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipMemcpyAsync(c->tbl.p, c->tbl_saved.p, c->tbl.bytes, hipMemcpyDeviceToDevice, c->stream));
-        write_spread_cfg(c);      // (the snapshot holds the topology spread weight of its save)
+        write_spread_cfg(c);      // (the snapshot holds the topology spread weight of its save, and the
+                                  // address of the (app, node) counts of its save)
+        c->hc_valid = false;      // (rebuilt from the mirror reinstated below, spec S15)
         c->m = c->m_saved;        // the mirror of the snapshot
         c->zero_alloc = count_zero_alloc(c->m);
         c->mirror_stale = false;

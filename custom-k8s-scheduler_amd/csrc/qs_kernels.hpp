@@ -173,10 +173,48 @@ __device__ __forceinline__ const uint8_t *soft_zone_bytes(const DevTable &t, uin
     return zs;
 }
 
+// Hostname topology spread (spec S15; pod-flag bit 15, the kind bits of such a pod are 0 like a soft
+// pod's, max_skew in bits 26-30).  The device keeps a uint16 count per (app, node), hcount[app * cap +
+// node], in an allocation of its own that exists only once a context has met such a pod; its address
+// sits in words 2-3 of the row that holds Wpts (null: not kept), so neither DevTable nor any kernel's
+// arguments change.  Per pod: the minimum m of the app's counts over every node of the table (a
+// reduction of its own in the pre-pass, feasible or not), then node i passes iff cnt(i) + 1 - m <= skew.
+// The minimum travels inverted, kHsInv - cnt >= 1 per real node, so that it is a maximum, 0 is the
+// neutral element of idle lanes and of the reset word, and the DPP wave maximum serves.
+constexpr uint32_t kHsInv = 0x10000u;
+// pod-flag bit 7 (free in the record): set by the score path's launcher in its by-value copy of the pod
+// for the launch of k_score_podg_max that takes the minimum and nothing else
+constexpr uint32_t kHsMinPass = 1u << 7;
+__host__ __device__ __forceinline__ bool pod_hostspread(uint32_t flags) { return ((flags >> 15) & 1u) != 0; }
+__device__ __forceinline__ uint16_t *aa_hcount(const DevTable &t) {
+    return *reinterpret_cast<uint16_t *const *>(t.zcount + (kMaxApps + 4) * kMaxZones + 2);
+}
+// k_persistent<..., HOST>: the apps of the stream's hostname-spread pods, words 16 .. 16 + kHostSpreadApps - 1
+// of the same row (entry j = app id of LDS slot j, -1 = unused; written by the host before the launch)
+__device__ __forceinline__ const int32_t *aa_host_row(const DevTable &t) {
+    return t.zcount + (kMaxApps + 4) * kMaxZones + 16;
+}
+// The app's count row of a hostname-spread pod, nullptr for every other pod (wave-uniform).
+__device__ __forceinline__ const uint16_t *hs_row(const DevTable &t, uint32_t flags) {
+    if (!pod_hostspread(flags)) return nullptr;
+    const uint16_t *h = aa_hcount(t);
+    return h ? h + (size_t)pod_app(flags) * t.cap : nullptr;
+}
+// cnt + 1 - m <= skew with inv = kHsInv - m, in unsigned arithmetic without a subtraction
+__device__ __forceinline__ bool hs_ok(uint32_t cnt, uint32_t inv, uint32_t flags) {
+    return cnt + 1u + inv <= pod_skew(flags) + kHsInv;
+}
+
 // SOFT (kFeatAA classes only): the instantiation of a stream that holds soft-spread pods (spec S14,
 // kFeatSoft), with node caps of its own (persistent_cap); every other stream runs the code it ran
 // before the score existed.
-template <int NPT, int BS, uint32_t F, bool SOFT = false>
+// HOST (kFeatAA classes only, never with SOFT): the instantiation of a stream that holds hostname-spread
+// pods (spec S15, kFeatHost).  It keeps the (app, node) counts of up to kHostSpreadApps apps of the stream in
+// LDS, uint16 hc[slot][node], loaded at entry from the (valid) global array; only the lane that owns a
+// node ever reads or writes its counts, so program order is all the ordering they need.  The global
+// array is NOT kept by this kernel: the host marks it stale after every PERSISTENT run and rebuilds it
+// from its mirror before the next launch that reads it.
+template <int NPT, int BS, uint32_t F, bool SOFT = false, bool HOST = false>
 __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__restrict__ pods,
                                                    const DPodX *__restrict__ podx, uint32_t P,
                                                    DevCfg c, int32_t *__restrict__ out_node,
@@ -261,6 +299,35 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
         }
         __syncthreads();
     }
+    // HOST: the LDS counts, the app -> slot map (0xFF: none) and the waves' inverted minima by the
+    // pod's parity (like redn)
+    [[maybe_unused]] uint16_t *hcl = nullptr;
+    [[maybe_unused]] uint8_t *hslot = nullptr;
+    [[maybe_unused]] uint32_t (*redh)[NW] = nullptr;
+    if constexpr ((F & kFeatAA) != 0 && HOST) {
+        static_assert(!SOFT, "a stream with soft and hostname-spread pods runs SCAN");
+        __shared__ uint16_t hcs[kHostSpreadApps * NPT * BS];
+        __shared__ uint8_t hsl[kMaxApps];
+        __shared__ uint32_t rh[2][NW];
+        hcl = hcs;
+        hslot = hsl;
+        redh = rh;
+        for (uint32_t a = tid; a < kMaxApps; a += BS) hslot[a] = 0xFFu;
+        __syncthreads();
+        const uint16_t *hg = aa_hcount(t);
+        const int32_t *ha = aa_host_row(t);
+        for (uint32_t j = 0; j < kHostSpreadApps; ++j) {
+            const int32_t a = ha[j];  // (uniform)
+            const bool av = a >= 0 && a < (int32_t)kMaxApps;
+            if (av && tid == 0) hslot[a] = (uint8_t)j;
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) {
+                const uint32_t idx = tid + k * BS;  // (this thread's nodes: nobody else reads these cells)
+                hcl[j * (NPT * BS) + idx] = (av && hg && idx < n) ? hg[(size_t)a * t.cap + idx] : (uint16_t)0;
+            }
+        }
+        __syncthreads();
+    }
     PodT<F> pn = pods[0];
     for (uint32_t s = 0; s < P; ++s) {
         const PodT<F> p = pn;
@@ -306,6 +373,35 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
                     const uint32_t wd = idx < n ? aw[idx] : 0u;
                     aam &= ~(((wd >> (app & 31u)) & 1u) << k);
                 }
+            }
+        }
+        // hostname-spread pods (spec S15; the pod record is workgroup-uniform, so is this branch): the
+        // minimum of the app's counts over EVERY node of the table, each thread over its own nodes (an
+        // idle node slot contributes the neutral 0 of the inverted form), a DPP wave maximum, one word
+        // per wave and a barrier of this pod's own; then the skew test joins the mask, ahead of the
+        // normalize pre-pass and the key pass alike.  An app without a slot is allowed nothing (the host
+        // lists every hostname-spread pod's app and keeps larger streams off this kernel).
+        if constexpr ((F & kFeatAA) != 0 && HOST) {
+            if (pod_hostspread(p.flags)) {
+                const uint32_t sl = hslot[pod_app(p.flags)];
+                const uint16_t *row = hcl + (sl & (kHostSpreadApps - 1u)) * (NPT * BS);
+                uint32_t cn[NPT], lh = 0;
+#pragma unroll
+                for (int k = 0; k < NPT; ++k) {
+                    const uint32_t idx = tid + k * BS;
+                    cn[k] = row[idx];
+                    const uint32_t u = idx < n ? kHsInv - cn[k] : 0u;
+                    lh = u > lh ? u : lh;
+                }
+                lh = wave_max_u32(lh);
+                if (lane == 0) redh[s & 1][w] = lh;
+                __syncthreads();
+                uint32_t hm = 0;
+#pragma unroll
+                for (int i = 0; i < NW; ++i) hm = redh[s & 1][i] > hm ? redh[s & 1][i] : hm;
+#pragma unroll
+                for (int k = 0; k < NPT; ++k)
+                    if (!(sl < kHostSpreadApps && hs_ok(cn[k], hm, p.flags))) aam &= ~(1u << k);
             }
         }
         uint32_t mt = 0, ma = 0;
@@ -426,6 +522,16 @@ __global__ __launch_bounds__(BS) void k_persistent(DevTable t, const PodT<F> *__
                 if (last >= 0) b[last] += 1;
                 spc[kSpcLast] = cell;
             }
+            // HOST (spec S15): the winner's owning thread bumps the LDS count of every placed pod whose
+            // app has a slot, whatever its kind
+            if constexpr (HOST) {
+                const uint32_t sl = hslot[app];
+                if (ks != 0 && sl < kHostSpreadApps) {
+#pragma unroll
+                    for (int k = 0; k < NPT; ++k)
+                        if (tid + k * BS == win) hcl[sl * (NPT * BS) + win] += 1;
+                }
+            }
             prev_app = app;
             prev_bit = 0;
             if (ks != 0) {
@@ -473,6 +579,9 @@ struct ScanScratch {
     // soft-spread pods (spec S14): the feasible-zones word of k_scan_norm, reset with mt / ma.  Behind
     // the partials, so that every older member stays where the kernels without kFeatAA address it.
     unsigned long long fz;
+    // hostname-spread pods (spec S15): the inverted minimum of the app's node counts (k_scan_norm; 0 =
+    // none), reset with fz
+    uint32_t hmin;
 };
 static_assert(offsetof(ScanScratch, lo) == offsetof(ScanHead, lo) && offsetof(ScanScratch, mt) == offsetof(ScanHead, mt),
               "ScanHead mirrors ScanScratch");
@@ -494,6 +603,9 @@ template <uint32_t F>
 __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__restrict__ pods,
                                                    const DPodX *__restrict__ podx, uint32_t s,
                                                    ScanScratch *sc) {
+    // (kFeatAA classes: bit 31 of s marks the launch that takes a hostname-spread pod's minimum, below)
+    [[maybe_unused]] bool minpass = false;
+    if constexpr ((F & kFeatAA) != 0) { minpass = (s >> 31) != 0; s &= 0x7FFFFFFFu; }
     const PodT<F> p = pods[s];
     // (a kFeatAA class without the normalizing plugins runs this pre-pass for soft-spread pods only,
     // spec S14, and has no extension records)
@@ -505,13 +617,37 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
     [[maybe_unused]] uint64_t lz = 0;      // soft-spread pods: the zones of this lane's feasible nodes (spec S14)
     [[maybe_unused]] bool soft = false;
-    if constexpr ((F & kFeatAA) != 0) { zw = spread_word(t, p.flags); soft = pod_soft(p.flags); }
+    // hostname-spread pods (spec S15): the app's count row and this lane's inverted minimum over ITS
+    // nodes, feasible or not (real nodes only: the loop runs below t.n, and a lane without a node keeps
+    // 0).  The skew test needs the finished minimum, so such a pod runs this kernel once for the minimum
+    // alone (minpass, the launcher's mark) and, in a normalizing class, once more for the maxima over
+    // the nodes that pass the skew test too.
+    [[maybe_unused]] const uint16_t *hc = nullptr;
+    [[maybe_unused]] uint32_t lh = 0, hm = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        zw = spread_word(t, p.flags);
+        soft = pod_soft(p.flags);
+        hc = hs_row(t, p.flags);
+        if (hc && !minpass) hm = sc->hmin;
+    }
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+        if constexpr ((F & kFeatAA) != 0) {
+            f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+            if (hc) {
+                const uint32_t cnt = hc[i];
+                if (minpass) {  // the minimum's launch: every node counts, nothing else is reduced
+                    const uint32_t u = kHsInv - cnt;
+                    lh = u > lh ? u : lh;
+                    f = false;
+                } else {
+                    f = f && hs_ok(cnt, hm, p.flags);
+                }
+            }
+        }
         if (f) {
             const uint32_t a = taint_raw(x, px), b = affinity_raw(x, p, px);
             lt = a > lt ? a : lt;
@@ -526,12 +662,14 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
     la = wave_max_u32(la);
     if constexpr ((F & kFeatAA) != 0) {
         if (soft) lz = wave_or_u64(lz);  // (the loop is over: every lane is active again)
+        if (hc) lh = wave_max_u32(lh);   // (hc is wave-uniform)
     }
     if ((threadIdx.x & 63) == 0) {
         if (lt) atomicMax(&sc->mt, lt);
         if (la) atomicMax(&sc->ma, la);
         if constexpr ((F & kFeatAA) != 0) {
             if (lz) atomicOr(&sc->fz, (unsigned long long)lz);  // one per wave
+            if (lh) atomicMax(&sc->hmin, lh);
         }
     }
 }
@@ -557,12 +695,22 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
         zs = soft_zone_bytes<4>(t, p.flags, pod_soft(p.flags) ? sc->fz : 0ull);
         if (zs) wpts = aa_wpts(t);
     }
+    // hostname-spread pods (spec S15): the app's count row and k_scan_norm's inverted minimum
+    [[maybe_unused]] const uint16_t *hc = nullptr;
+    [[maybe_unused]] uint32_t hm = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        hc = hs_row(t, p.flags);
+        if (hc) hm = sc->hmin;
+    }
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
         const RowT<F> r = load_row<F>(t, i);
         const RowX x = load_rowx<F>(t, i);
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+        if constexpr ((F & kFeatAA) != 0) {
+            f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+            if (hc) f = f && hs_ok(hc[i], hm, p.flags);
+        }
         uint32_t sco[4];
         // (kFeatAA classes: the scores always go to the local array, which then stays in registers;
         // the pointer select of the older classes keeps their heavier scorers' array in scratch)
@@ -683,7 +831,7 @@ __global__ __launch_bounds__(256) void k_scan_commit(DevTable t, const PodT<F> *
     sc->best = nblk ? ks : 0ull;
     sc->mt = 0;
     sc->ma = 0;
-    if constexpr ((F & kFeatAA) != 0) sc->fz = 0;
+    if constexpr ((F & kFeatAA) != 0) { sc->fz = 0; sc->hmin = 0; }
     if (!out_node) return;
     const PodT<F> p = pods[s];
     if (ks) {
@@ -705,6 +853,9 @@ __global__ __launch_bounds__(256) void k_scan_commit(DevTable t, const PodT<F> *
             uint32_t *wp = t.apps + (size_t)(app >> 5) * t.cap + w;
             *wp = *wp | (1u << (app & 31u));
             t.zcount[app * kMaxZones + (uint32_t)t.zone[w]] += 1;
+            // ... and in the (app, node) counts of spec S15 where the context keeps them
+            uint16_t *hcn = aa_hcount(t);
+            if (hcn) hcn[(size_t)app * t.cap + w] += 1;
         }
     }
     out_node[s] = ks ? (int32_t)key_node(ks) : -1;
@@ -855,7 +1006,18 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     uint32_t mt = 0, ma = 0;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
     [[maybe_unused]] uint64_t lz = 0;      // soft-spread pods: the zone of this lane's node if feasible (spec S14)
-    if constexpr ((F & kFeatAA) != 0) zw = spread_word(t, p.flags);
+    // hostname-spread pods (spec S15), as in k_scan_norm: a launch for the inverted minimum over every
+    // node of the table (kHsMinPass in the launcher's copy of the pod; a thread without a node keeps 0),
+    // and in a normalizing class one more for the maxima under the skew test
+    [[maybe_unused]] const uint16_t *hc = nullptr;
+    [[maybe_unused]] uint32_t lh = 0, hm = 0;
+    [[maybe_unused]] bool minpass = false;
+    if constexpr ((F & kFeatAA) != 0) {
+        zw = spread_word(t, p.flags);
+        hc = hs_row(t, p.flags);
+        minpass = (p.flags & kHsMinPass) != 0;
+        if (hc && !minpass) hm = (uint32_t)__hip_atomic_load(gs + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (i < n) {
         RowT<F> r;
         RowX x;
@@ -866,7 +1028,18 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
             x = load_rowx<F>(t, i);
         }
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+        if constexpr ((F & kFeatAA) != 0) {
+            f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+            if (hc) {
+                const uint32_t cnt = hc[i];
+                if (minpass) {
+                    lh = kHsInv - cnt;
+                    f = false;
+                } else {
+                    f = f && hs_ok(cnt, hm, p.flags);
+                }
+            }
+        }
         if (f) {
             mt = taint_raw(x, px);
             ma = affinity_raw(x, p, px);
@@ -880,12 +1053,14 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     ma = wave_max_u32(ma);
     if constexpr ((F & kFeatAA) != 0) {
         if (pod_soft(p.flags)) lz = wave_or_u64(lz);
+        if (hc) lh = wave_max_u32(lh);
     }
     if ((threadIdx.x & 63) == 0) {  // one atomic per wave (words stay zero between calls)
         if (mt) __hip_atomic_fetch_max(gs + 2, (uint64_t)mt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (ma) __hip_atomic_fetch_max(gs + 3, (uint64_t)ma, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr ((F & kFeatAA) != 0) {
             if (lz) __hip_atomic_fetch_or(gs + 4, lz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lh) __hip_atomic_fetch_max(gs + 5, (uint64_t)lh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -913,6 +1088,13 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
                 reinterpret_cast<int32_t *>(hout + score_pack_bytes(n))[lane] = zs[lane] == kNoZoneScore ? -1 : (int32_t)zs[lane];
         }
     }
+    // hostname-spread pods (spec S15): the app's count row and k_score_podg_max's inverted minimum (gs[5])
+    [[maybe_unused]] const uint16_t *hc = nullptr;
+    [[maybe_unused]] uint32_t hm = 0;
+    if constexpr ((F & kFeatAA) != 0) {
+        hc = hs_row(t, p.flags);
+        if (hc) hm = (uint32_t)__hip_atomic_load(gs + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (blockIdx.x == 0 && tid == 0 && pidx < n) set_row(t, pidx, prow);
     uint32_t mt = 0, ma = 0;
     if constexpr ((F & kFeatNorm) != 0) {  // k_score_podg_max's maxima (the previous launch)
@@ -930,7 +1112,10 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
             x = load_rowx<F>(t, i);
         }
         bool f = feasible<F>(r, x, p, px);
-        if constexpr ((F & kFeatAA) != 0) f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+        if constexpr ((F & kFeatAA) != 0) {
+            f = f && aa_ok(t, p.flags, i) && spread_ok(t, p.flags, zw, i);
+            if (hc) f = f && hs_ok(hc[i], hm, p.flags);
+        }
         uint32_t sco[4];
         uint32_t tot = node_total<F>(r, x, p, px, c, mt, rcp_exact(mt), ma, rcp_exact(ma), sco);
         if constexpr ((F & kFeatAA) != 0) {
@@ -959,7 +1144,10 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
                 __hip_atomic_store(gs + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(gs + 3, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if constexpr ((F & kFeatAA) != 0) __hip_atomic_store(gs + 4, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr ((F & kFeatAA) != 0) {
+                __hip_atomic_store(gs + 4, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(gs + 5, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             *reinterpret_cast<volatile uint64_t *>(hout) = b;
             __threadfence_system();
             __hip_atomic_store(reinterpret_cast<uint64_t *>(hout + 8), seq, __ATOMIC_RELEASE,
@@ -4765,11 +4953,11 @@ __global__ __launch_bounds__(64 * kClaimWaves) void k_batch_claim(
 // =============================================================================================
 #define QS_RET(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-template <int NPT, int BS, uint32_t F, bool SOFT = false>
+template <int NPT, int BS, uint32_t F, bool SOFT = false, bool HOST = false>
 static hipError_t persistent_t(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st,
                                hipStream_t stream) {
-    hipLaunchKernelGGL((k_persistent<NPT, BS, F, SOFT>), dim3(1), dim3(BS), 0, stream, t,
+    hipLaunchKernelGGL((k_persistent<NPT, BS, F, SOFT, HOST>), dim3(1), dim3(BS), 0, stream, t,
                        (const PodT<F> *)pods, podx, P, c, on, ok, st);
     return hipGetLastError();
 }
@@ -4777,7 +4965,7 @@ static hipError_t persistent_t(const DevTable &t, const void *pods, const DPodX 
 // Largest node count per feature set for the register-resident rows (1024 threads, 4 waves/SIMD;
 // the largest NPT of each set spills a few dwords to scratch: correct, slower — the LOOKAHEAD
 // engine is the fast path at these sizes).  Wide rows carry three f64 memory columns.
-template <uint32_t F, bool SOFT = false>
+template <uint32_t F, bool SOFT = false, bool HOST = false>
 static constexpr uint32_t persistent_cap() {
     // anti-affinity classes (kFeatAA): a zone register per node beside the rows, and no spill at all
     // (tests/test_antiaffinity_cpu.py reads the code objects): see DESIGN.md §3.4 for the budget
@@ -4788,6 +4976,9 @@ static constexpr uint32_t persistent_cap() {
             if (F & kFeatWide) return (F & kFeatNorm) ? 1024u : 2048u;
             return (F & kFeatNorm) ? 1024u : (F & kFeatRes) ? 2048u : 3072u;
         }
+        // the instantiations with the hostname-spread counts (spec S15): the compact
+        // normalizing class spills at two nodes per lane, every other class keeps its cap
+        if (HOST && !(F & kFeatWide) && (F & kFeatNorm)) return 1024u;
         if (F & kFeatWide) return (F & kFeatNorm) ? 1024u : 2048u;
         return (F & (kFeatNorm | kFeatRes)) ? 2048u : 3072u;
     }
@@ -4795,31 +4986,31 @@ static constexpr uint32_t persistent_cap() {
     return F == 0 ? 6144u : (F == kFeatExt ? 5120u : 2048u);
 }
 
-template <uint32_t F, bool SOFT = false>
+template <uint32_t F, bool SOFT = false, bool HOST = false>
 static hipError_t persistent_f(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st,
                                hipStream_t stream) {
     const uint32_t n = t.n;
-    if (n > persistent_cap<F, SOFT>()) return hipErrorInvalidValue;
-    if (n <= 64) return persistent_t<1, 64, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 128) return persistent_t<1, 128, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 256) return persistent_t<1, 256, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 512) return persistent_t<1, 512, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
-    if (n <= 1024) return persistent_t<1, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
-    if constexpr (persistent_cap<F, SOFT>() > 1024) {
-        if (n <= 2048) return persistent_t<2, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n > persistent_cap<F, SOFT, HOST>()) return hipErrorInvalidValue;
+    if (n <= 64) return persistent_t<1, 64, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 128) return persistent_t<1, 128, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 256) return persistent_t<1, 256, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 512) return persistent_t<1, 512, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
+    if (n <= 1024) return persistent_t<1, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT, HOST>() > 1024) {
+        if (n <= 2048) return persistent_t<2, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F, SOFT>() > 2048) {
-        if (n <= 3072) return persistent_t<3, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT, HOST>() > 2048) {
+        if (n <= 3072) return persistent_t<3, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F, SOFT>() > 3072) {
-        if (n <= 4096) return persistent_t<4, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT, HOST>() > 3072) {
+        if (n <= 4096) return persistent_t<4, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F, SOFT>() > 4096) {
-        if (n <= 5120) return persistent_t<5, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT, HOST>() > 4096) {
+        if (n <= 5120) return persistent_t<5, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
     }
-    if constexpr (persistent_cap<F, SOFT>() > 5120) {
-        if (n <= 6144) return persistent_t<6, 1024, F, SOFT>(t, pods, podx, P, c, on, ok, st, stream);
+    if constexpr (persistent_cap<F, SOFT, HOST>() > 5120) {
+        if (n <= 6144) return persistent_t<6, 1024, F, SOFT, HOST>(t, pods, podx, P, c, on, ok, st, stream);
     }
     return hipErrorInvalidValue;
 }
@@ -4838,7 +5029,11 @@ static hipError_t scan_pod_f(const DevTable &t, const void *pods_, const DPodX *
     // classes without a normalizing plugin too, and on a table that keeps the column-major copy it
     // goes through the row kernels (which stride over any grid) with the grid of the column scan, so
     // the commit reduces the partials it reduces for every other pod.
-    const bool softp = (F & kFeatAA) != 0 && (part & 128) != 0;
+    // part & 256: pod s is a hostname-spread pod (spec S15).  The same route, and the pre-pass first
+    // runs once for the minimum of the app's node counts (a normalizing class then runs it again for
+    // its maxima, which need the skew test).
+    const bool hsp = (F & kFeatAA) != 0 && (part & 256) != 0;
+    const bool softp = (F & kFeatAA) != 0 && (part & (128 | 256)) != 0;
     // one partial key per block; a grid of <= 2048 blocks (8 four-wave blocks per CU) strides
     const uint32_t units = soa ? (t.n + 3) / 4 : t.n;
     uint32_t blocks = min(kScanBlocksMax, max(1u, (units + 255) / 256));
@@ -4864,7 +5059,10 @@ static hipError_t scan_pod_f(const DevTable &t, const void *pods_, const DPodX *
             }
         }
         if (!soa || softp) {
-            if ((F & kFeatNorm) || softp)
+            if (hsp)
+                hipLaunchKernelGGL((k_scan_norm<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx,
+                                   s | 0x80000000u, sc);
+            if ((F & kFeatNorm) || (softp && !hsp))
                 hipLaunchKernelGGL((k_scan_norm<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx, s, sc);
             hipLaunchKernelGGL((k_scan_key<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx, s, c, sc,
                                feas, score, total);
@@ -4900,6 +5098,15 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
     if ((F & kFeatNorm) && podx) px = *podx;
     if (gs && t.n > 0) {
         const uint32_t g = (t.n + kScorePodGT - 1) / kScorePodGT;
+        if constexpr ((F & kFeatAA) != 0) {
+            // a hostname-spread pod (spec S15): first the minimum of its app's node counts, alone
+            if (pod_hostspread(p.flags)) {
+                PodT<F> pm = p;
+                pm.flags |= kHsMinPass;
+                hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, pm, px, gs, pidx,
+                                   prow);
+            }
+        }
         if constexpr ((F & kFeatNorm) != 0) {
             hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, p, px, gs, pidx,
                                prow);
@@ -4915,7 +5122,8 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
     }
     if constexpr ((F & kFeatAA) != 0) {
         // the single-workgroup form carries no zone scores (the host always passes the device words)
-        if (pod_soft(p.flags)) return hipErrorInvalidValue;
+        // ... and no minimum of a hostname-spread pod's node counts (spec S15)
+        if (pod_soft(p.flags) || pod_hostspread(p.flags)) return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL((k_score_pod1<F>), dim3(1), dim3(1024), 0, stream, t, p, px, c, hout, seq, pidx, prow);
     return hipGetLastError();

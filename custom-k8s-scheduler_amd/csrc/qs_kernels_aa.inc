@@ -33,12 +33,32 @@ __global__ void k_aa_apply(DevTable t, uint32_t node, uint32_t app, int32_t sign
     if (sign > 0) *wp = *wp | bit;
     else if (clear_bit) *wp = *wp & ~bit;
     atomicAdd(&t.zcount[app * kMaxZones + (uint32_t)t.zone[node]], sign > 0 ? 1 : -1);
+    // ... and the (app, node) count of spec S15 where the context keeps them (the host has checked that
+    // an Unreserve finds a recorded pod)
+    uint16_t *hc = aa_hcount(t);
+    if (hc) {
+        uint16_t *cp = hc + (size_t)app * t.cap + node;
+        *cp = (uint16_t)(*cp + (sign > 0 ? 1 : -1));
+    }
+}
+
+// The (app, node) counts rebuilt from the host mirror's sparse map (spec S15): the array has been
+// zeroed; entry k goes to cell idx[k] (= app * cap + node, below `cells`).
+__global__ void k_hc_scatter(uint16_t *hc, const uint32_t *idx, const uint16_t *val, uint32_t m, uint32_t cells) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < m && idx[k] < cells) hc[idx[k]] = val[k];
 }
 #endif
 
 hipError_t QS_AA_FN(persistent)(const DevTable &t, const void *pods, const DPodX *podx, uint32_t P,
                                 const DevCfg &c, int32_t *on, uint64_t *ok, uint64_t *st, hipStream_t stream) {
     if (!t.apps) return hipErrorInvalidValue;
+    if (c.feat & kFeatHost) {  // the stream holds hostname-spread pods (spec S15) and no soft pod
+        if (c.feat & kFeatSoft) return hipErrorInvalidValue;
+        if (c.feat & kFeatNorm) return persistent_f<kAN, false, true>(t, pods, podx, P, c, on, ok, st, stream);
+        if (c.feat & kFeatRes) return persistent_f<kAG, false, true>(t, pods, podx, P, c, on, ok, st, stream);
+        return persistent_f<kAD, false, true>(t, pods, podx, P, c, on, ok, st, stream);
+    }
     if (c.feat & kFeatSoft) {  // the stream holds soft-spread pods (spec S14)
         if (c.feat & kFeatNorm) return persistent_f<kAN, true>(t, pods, podx, P, c, on, ok, st, stream);
         if (c.feat & kFeatRes) return persistent_f<kAG, true>(t, pods, podx, P, c, on, ok, st, stream);
@@ -50,6 +70,9 @@ hipError_t QS_AA_FN(persistent)(const DevTable &t, const void *pods, const DPodX
 }
 
 uint32_t QS_AA_FN(persistent_max_nodes)(uint32_t feat) {
+    if (feat & kFeatHost)
+        return (feat & kFeatNorm) ? persistent_cap<kAN, false, true>()
+                                  : (feat & kFeatRes) ? persistent_cap<kAG, false, true>() : persistent_cap<kAD, false, true>();
     if (feat & kFeatSoft)
         return (feat & kFeatNorm) ? persistent_cap<kAN, true>()
                                   : (feat & kFeatRes) ? persistent_cap<kAG, true>() : persistent_cap<kAD, true>();

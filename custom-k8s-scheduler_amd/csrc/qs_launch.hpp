@@ -161,5 +161,7 @@ __global__ void k_set_row(DevTable t, uint32_t i, HostRow v, uint32_t feat);
 // Reserve (sign +1) / Unreserve (-1) of one pod of `app` on `node` in the anti-affinity state
 // (spec S12): sets the presence bit, or clears it when clear_bit, and moves the (app, zone) count.
 __global__ void k_aa_apply(DevTable t, uint32_t node, uint32_t app, int32_t sign, uint32_t clear_bit);
+// The (app, node) counts of spec S15 from the mirror's sparse map into the zeroed array.
+__global__ void k_hc_scatter(uint16_t *hc, const uint32_t *idx, const uint16_t *val, uint32_t m, uint32_t cells);
 
 }  // namespace qs

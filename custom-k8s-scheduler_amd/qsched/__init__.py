@@ -26,10 +26,10 @@ from ._abi import (ENGINES, ENGINE_NAMES, EXPORTED, LIB_PATH, POD_DTYPE, QS_ABI_
 __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_struct", "fit_error_message",
            "synth_generate", "shape_table", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
            "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH",
-           "aa_spread", "aa_spread_soft", "aa_is_soft", "aa_kind", "aa_max_skew", "QS_AA_SOFT", "QS_MAX_ZONES", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
+           "aa_spread", "aa_spread_soft", "aa_spread_hostname", "aa_is_soft", "aa_is_hostkey", "QS_AA_HOSTKEY", "aa_kind", "aa_max_skew", "QS_AA_SOFT", "QS_MAX_ZONES", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
            "QS_MAX_SPREAD_SKEW"]
 
-from ._abi import (QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
+from ._abi import (QS_AA_HOSTKEY, QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
                    QS_MAX_SPREAD_SKEW, QS_MAX_ZONES)
 
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
@@ -48,6 +48,18 @@ def aa_spread_soft(max_skew: int) -> int:
     S14): the pod is not filtered by spread; every feasible node's total gains the PodTopologySpread
     score of its zone times ``Scheduler.set_topology_spread_weight``."""
     return aa_spread(max_skew) | QS_AA_SOFT
+
+
+def aa_spread_hostname(max_skew: int) -> int:
+    """QS_AA_SPREAD_HOSTNAME(max_skew): topology spread with ``topologyKey: kubernetes.io/hostname`` and
+    ``whenUnsatisfiable: DoNotSchedule`` (spec S15): at most max_skew pods of the app more on any node
+    than on the emptiest node of the table.  max_skew 1..31."""
+    return aa_spread(max_skew) | QS_AA_HOSTKEY
+
+
+def aa_is_hostkey(anti_affinity):
+    """QS_AA_IS_HOSTKEY: the hostname-key flag (scalar or array)."""
+    return (anti_affinity >> 18) & 1
 
 
 def aa_is_soft(anti_affinity):

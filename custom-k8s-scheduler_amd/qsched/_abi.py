@@ -24,6 +24,7 @@ QS_MAX_ZONES = 64
 QS_AA_NONE, QS_AA_HOSTNAME, QS_AA_ZONE = 0, 1, 2
 QS_AA_SPREAD_ZONE, QS_MAX_SPREAD_SKEW = 3, 31  # spec S13: kind in the low byte, max_skew in bits 8-12
 QS_AA_SOFT = 1 << 16  # spec S14: ScheduleAnyway, with QS_AA_SPREAD_ZONE only
+QS_AA_HOSTKEY = 1 << 18  # spec S15: the spread key is the node, with QS_AA_SPREAD_ZONE only and without QS_AA_SOFT
 QS_MAX_SCORE_RES = 4
 # qs_fit_reason: FitError reason columns of qs_stream_fit_errors, with upstream's reason strings
 FIT_REASONS = ["Too many pods", "Insufficient cpu", "Insufficient memory", "Insufficient {ext0}",

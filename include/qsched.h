@@ -84,7 +84,16 @@ typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
  * (UP plugins/podtopologyspread Score / NormalizeScore): kind 3 with the flag QS_AA_SOFT above max_skew.
  * Such a pod is not filtered by spread; on a context that tracks, every feasible node's total gains
  * Wpts * PTS(zone of the node), PTS in 0..100 from the app's recorded pods per zone over the zones that
- * hold a node feasible for the pod (qs_set_topology_spread_weight; qs_score_pod_zone_scores). */
+ * hold a node feasible for the pod (qs_set_topology_spread_weight; qs_score_pod_zone_scores).
+ * QS_AA_SPREAD_HOSTNAME(max_skew) (spec S15) is the DoNotSchedule constraint with topologyKey
+ * kubernetes.io/hostname: kind 3 with the flag QS_AA_HOSTKEY, every node a domain of its own.  A node
+ * is infeasible when taking it would leave it more than max_skew pods of the app above the emptiest
+ * node of the table, whether the pod could take that node or not.  Exact streams run QS_ENGINE_PERSISTENT
+ * for up to 16 distinct such apps per stream and no QS_AA_SPREAD_SOFT pod in the same stream (beyond
+ * that AUTO runs SCAN and an explicit PERSISTENT returns QS_EINVAL) or QS_ENGINE_SCAN; the flag together with
+ * QS_AA_SOFT, or on another kind, is QS_EINVAL; QS_MODE_BATCHED refuses the stream.  The context keeps
+ * 2 KB of counts per node from the first such pod on: tables above 2^19 nodes, and tables with a node
+ * whose max_pods exceeds 65,535, refuse the pod (QS_EINVAL). */
 typedef enum qs_anti_affinity {
     QS_AA_NONE = 0, QS_AA_HOSTNAME = 1, QS_AA_ZONE = 2, QS_AA_SPREAD_ZONE = 3
 } qs_anti_affinity;
@@ -95,6 +104,9 @@ typedef enum qs_anti_affinity {
 #define QS_AA_SOFT ((int32_t)0x10000) /* only with QS_AA_SPREAD_ZONE: ScheduleAnyway (spec S14) */
 #define QS_AA_SPREAD_SOFT(max_skew) ((int32_t)(QS_AA_SPREAD(max_skew) | QS_AA_SOFT))
 #define QS_AA_IS_SOFT(x) ((int32_t)(((x) >> 16) & 1))
+#define QS_AA_HOSTKEY ((int32_t)0x40000) /* bit 18 (bit 17 alone stays invalid); only with QS_AA_SPREAD_ZONE, without QS_AA_SOFT: the spread key is the node (spec S15) */
+#define QS_AA_SPREAD_HOSTNAME(max_skew) ((int32_t)(QS_AA_SPREAD(max_skew) | QS_AA_HOSTKEY))
+#define QS_AA_IS_HOSTKEY(x) ((int32_t)(((x) >> 18) & 1))
 
 /* Scoring resources (spec/semantics.md S5 "Scoring resources"): cpu, memory, or one of the table's
  * two extended-resource columns (the caller interns e.g. "amd.com/gpu" as QS_RES_EXT0). */

@@ -12,6 +12,9 @@ Arms per table:
   spread_scan       DESIGN.md §3.5), checked against tests/spread_ref.py; read beside aa_* of the same run
   soft_persistent   the spread_* arms with the SPREAD(1) pods turned soft (zone topology spread scoring, spec S14,
   soft_scan         DESIGN.md §3.6), checked against tests/soft_spread_ref.py; read beside spread_* of the same run
+  hostspread_persistent  the aa_* arms with the HOSTNAME apps' pods turned into HOSTSPREAD(1) (hostname topology
+  hostspread_scan   spread, spec S15), checked against tests/hostspread_ref.py; read beside aa_*
+                    of the same run: the same pods under the one-per-node rule
   plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
   plain_scan        the cost of the filter and the recording is aa_* against plain_*
 
@@ -30,7 +33,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "soft_persistent", "soft_scan",
-        "plain_persistent", "plain_scan"]
+        "hostspread_persistent", "hostspread_scan", "plain_persistent", "plain_scan"]
 
 
 def paths(tree):
@@ -50,7 +53,13 @@ def run_arm(n, p, arm, steps, prefix):
     nodes, pods = A.fold(nodes, pods, 40, 4)
     soft = arm.startswith("soft_")
     spread = arm.startswith("spread_") or soft
-    tracked = arm.startswith("aa_") or spread
+    host = arm.startswith("hostspread_")
+    tracked = arm.startswith("aa_") or spread or host
+    if host:
+        import hostspread_ref as H
+
+        pods = pods.copy()
+        pods["anti_affinity"][pods["anti_affinity"] == A.HOSTNAME] = H.spread_hostname(1)
     if spread:
         import spread_ref as S
 
@@ -84,7 +93,9 @@ def run_arm(n, p, arm, steps, prefix):
             return out
         pl, keys = head.results()
         head.free()
-        if soft:
+        if host:
+            ref = H.run(nodes, pods[:prefix])
+        elif soft:
             ref = R.run(nodes, pods[:prefix])
         elif spread:
             ref = S.run(nodes, pods[:prefix])
