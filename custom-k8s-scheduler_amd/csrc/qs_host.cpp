@@ -37,6 +37,55 @@ using namespace qs_host;
 
 namespace {
 
+// ---- environment knobs of the stream-run path (qs_stream_run and its engines) ----------------------
+// Every getenv of that path is here.  (The score path's QS_UNPACK_* / QS_SCORE_DIAG and QS_FORCE_RES
+// stay with their code.)
+char env_char(const char *name) {  // the value's first character; 0: unset or empty
+    const char *e = getenv(name);
+    return e ? e[0] : 0;
+}
+bool env_is(const char *name, char v) { return env_char(name) == v; }
+int env_int(const char *name) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : 0;
+}
+
+// Read once per process, on first use: tests and tools set these from outside the process only.
+struct ProcKnobs {
+    bool overlap_off = env_is("QS_LA_OVERLAP", '0');          // 0: serial lookahead windows
+    bool resolver_waves1 = env_is("QS_RESOLVER_WAVES", '1');  // 1: single-wave resolver (serial windows)
+    bool diag = env_is("QS_DIAG", '1');                       // 1: diagnostic resolver, shader-clock stamps on stderr
+    bool handoff_off = env_is("QS_HANDOFF", '0');             // 0: cross-stream events, no in-kernel window hand-off
+    char graph = env_char("QS_GRAPH");  // '1': force graph replay (sharded and hand-off runs too); '0': never capture
+    // n: a host sync every n windows / batches (profiling aid: bounds the launches in flight under counter
+    // collection).  Clamped to >= 0: batched mode used to cast a negative n to a period of 2^32 - |n|, which
+    // no reachable batch count is a multiple of, so it never synced either.
+    uint32_t sync_every = (uint32_t)std::max(0, env_int("QS_SYNC_EVERY"));
+    uint32_t res_sel = (uint32_t)std::max(0, env_int("QS_RES_SEL"));  // n > 0: selector workgroups of the resident launch
+    bool res_diag = [] {  // 1 | 2: the resident resolver's time split on stderr (the digit itself: RunKnobs::sel_diag)
+        const char d = env_char("QS_RES_DIAG");
+        return d == '1' || d == '2';
+    }();
+};
+const ProcKnobs &proc_knobs() {
+    static const ProcKnobs k;
+    return k;
+}
+
+// Read at the start of every run: tests and A/B timing switch these per case inside one process.
+struct RunKnobs {
+    bool norm_waves1 = env_is("QS_NORM_WAVES", '1');            // 1: single-wave normalizing resolver
+    bool resident_off = env_is("QS_RESIDENT", '0');             // 0: per-window launches
+    bool res_k32_off = env_is("QS_RES_K32", '0');               // 0: the resident resolver's 64-bit key path
+    bool fast_alloc_off = env_is("QS_FAST_ALLOC", '0');         // 0: generic scorers (zero-allocatable terms kept)
+    bool res_uniform_off = env_is("QS_RES_UNIFORM", '0');       // 0: no uniform windows
+    bool fused_merge_off = env_is("QS_BATCH_FUSED_MERGE", '0');  // 0: batched mode's separate k_la_merge launch
+    const char *inject = getenv("QS_INJECT_FAULT");             // test hooks (inject_once; tests/test_gpu_recovery.py)
+    bool hosttime = getenv("QS_HOSTTIME") != nullptr;           // set: the lookahead enqueue's host time on stderr
+    bool norm_diag = getenv("QS_NORM_DIAG") != nullptr;         // set: rescans and resumed windows on stderr
+    bool sel_diag = env_is("QS_RES_DIAG", '1');                 // 1 (not 2): the selectors stamp too
+};
+
 uint32_t feat_of(const qs_config &c) {
     uint32_t f = 0;
     if (c.enable_taint) f |= kFeatTaint;
@@ -787,16 +836,16 @@ void put_row(Mirror &m, uint32_t i, const RowSnap &r) {
 
 // Test hooks for the recovery path (tests/test_gpu_recovery.py): QS_INJECT_FAULT=<entry> makes the
 // next call of that entry point fail as a device error after its device work.  One-shot per
-// context and hook (the environment itself is never modified by the library).
+// context and hook (the environment itself is never modified by the library).  `e` is the run's
+// RunKnobs::inject.
 enum InjectHook : uint32_t { kInjStreamRun = 1u, kInjHandoff = 2u, kInjResidentStall = 4u };
-bool inject_once(qs_ctx *c, const char *name, uint32_t bit) {
-    const char *e = getenv("QS_INJECT_FAULT");
+bool inject_once(qs_ctx *c, const char *e, const char *name, uint32_t bit) {
     if (!e || std::strcmp(e, name) != 0 || (c->inject_used & bit)) return false;
     c->inject_used |= bit;
     return true;
 }
-void maybe_inject_fault(qs_ctx *c, const char *entry) {
-    if (inject_once(c, entry, kInjStreamRun))
+void maybe_inject_fault(qs_ctx *c, const char *e, const char *entry) {
+    if (inject_once(c, e, entry, kInjStreamRun))
         fail(QS_EDEVICE, std::string("injected device fault in ") + entry);
 }
 
@@ -918,8 +967,7 @@ int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host
 // Overlapped windows (select of window w+1 beside resolve of window w): on unless
 // cfg.lookahead_serial or QS_LA_OVERLAP=0; needs 2K <= 64 dirty slots, i.e. K <= 32.
 bool la_overlap(const qs_ctx *c) {
-    static const char *env = getenv("QS_LA_OVERLAP");
-    if (env && env[0] == '0') return false;
+    if (proc_knobs().overlap_off) return false;
     return !c->cfg.lookahead_serial && la_window(c) <= 32;
 }
 
@@ -948,15 +996,92 @@ void percentile_stats(const std::vector<uint64_t> &st, qs_stats *s) {
     s->max_cycle_us = d.back();
 }
 
-}  // namespace
+// =============================================================================================
+// qs_stream_run: the run's plan, one function per engine, the post-run step
+// =============================================================================================
+
+// What one stream run does.  plan_run is the only place that sets c->dc.feat for a stream run.
+struct RunPlan {
+    int eng;           // the qs_engine that runs
+    uint32_t feat;     // c->dc.feat of the run
+    bool aa_exact;     // an exact stream of a tracking context: it carries the filter and records its pods
+    bool spread_over;  // more SPREAD apps than k_persistent keeps zone counts for
+    bool host_spread;  // the stream holds hostname-spread pods (and the context tracks)
+    bool host_over;    // ... of more apps than k_persistent's slots, or beside soft-spread pods
+};
+
+RunPlan plan_run(qs_ctx *c, const qs_stream *s, qs_mode mode) {
+    RunPlan p{};
+    c->dc.feat = s->feat;
+    // pod anti-affinity (spec S12): every exact stream of a tracking context carries the filter
+    // and records its pods; batched mode filters and records by itself (S11, the same state)
+    p.aa_exact = c->aa_track && mode == QS_MODE_EXACT;
+    if (c->aa_track) aa_check_table(c);
+    if (p.aa_exact) {
+        c->dc.feat = aa_feat(s->feat);
+        // soft-spread pods (spec S14): the k_persistent instantiations that carry the score, and their caps
+        if (std::find(s->soft.begin(), s->soft.end(), 1) != s->soft.end()) c->dc.feat |= kFeatSoft;
+    }
+    // zone topology spread (spec S13): k_persistent keeps the counts of at most kSpreadApps apps
+    p.spread_over = p.aa_exact && s->spread_apps > kSpreadApps;
+    // hostname topology spread (spec S15): the k_persistent instantiations that keep the (app, node)
+    // counts of the stream's hostname-spread apps in LDS (kFeatHost), for at most kHostSpreadApps apps
+    // and no soft pod in the same stream
+    p.host_spread = p.aa_exact && s->host_pods != 0;
+    const bool has_soft = p.aa_exact && (c->dc.feat & kFeatSoft) != 0;
+    p.host_over = p.host_spread && (s->host_apps > kHostSpreadApps || has_soft);
+    if (p.host_spread && !p.host_over) c->dc.feat |= kFeatHost;
+    p.eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, c->m.n, p.spread_over, p.host_over);
+    p.feat = c->dc.feat;
+    return p;
+}
+
+// The device arrays a run reads and writes: the stream's pod records and its per-pod outputs.
+struct RunIo {
+    const void *dp;
+    const DPodX *dx;
+    int32_t *on;
+    uint64_t *ok;
+    uint64_t *st;  // config.record_timestamps, else nullptr
+};
+
+// A prepared stream's launch sequence as one HIP graph: replayed while `key` (every pointer and value
+// the captured launches were given) equals the key it was captured under, captured again otherwise.
+// enqueue(capturing) issues the sequence on c->stream.
+using GraphKey = std::vector<uint8_t>;
+void key_put(GraphKey &key, const void *p, size_t nb) {
+    key.insert(key.end(), (const uint8_t *)p, (const uint8_t *)p + nb);
+}
+template <class F>
+void replay_or_capture(qs_ctx *c, qs_stream *s, const GraphKey &key, F &&enqueue) {
+    if (!s->gexec || s->gkey != key) {
+        if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
+        s->gexec = nullptr;
+        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        try {
+            enqueue(true);
+        } catch (...) {
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(c->stream, &g);
+            if (g) (void)hipGraphDestroy(g);
+            throw;
+        }
+        hipGraph_t g = nullptr;
+        HIPCHK(hipStreamEndCapture(c->stream, &g));
+        const hipError_t ie = hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        HIPCHK(ie);
+        s->gkey = key;
+    }
+    HIPCHK(hipGraphLaunch(s->gexec, c->stream));
+}
 
 // QS_MODE_BATCHED (spec S11): batches of B <= 64 pods; per batch one select + merge (each pod's
 // 64 best keys against the batch-start table, anti-affinity included) and one claim kernel that
 // resolves the batch, applies it and builds the next one on the device.  The ceil(P/B) batches of
 // a stream are captured once as a HIP graph; the few pods still carried at the end (all their
 // candidates claimed by earlier pods of their batch) run in extra batches.  Returns the batch count.
-uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, int32_t *on, uint64_t *ok,
-                     KernelTimer &kt) {
+uint64_t run_batched(qs_ctx *c, qs_stream *s, const RunIo &io, const RunKnobs &kn, KernelTimer &kt) {
     const uint32_t n = c->m.n, P = s->p;
     for (int q = 0; q < 3; q++)
         if (c->strat[q].type != QS_STRATEGY_LEAST_ALLOCATED)
@@ -982,66 +1107,44 @@ uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, i
     uint32_t *ctrl = c->bctrl.as<uint32_t>(), *bidx = ctrl + 64, *tickets = ctrl + 128;
     LaBufs bf{c->lists.as<uint64_t>(), c->clists.as<uint64_t>(), nullptr, nullptr, nullptr, nullptr,
               nullptr, bidx, ctrl};
-    const char *fm = getenv("QS_BATCH_FUSED_MERGE");  // 0: the separate k_la_merge launch (read per run)
-    if (!(fm && fm[0] == '0')) bf.tickets = tickets;
+    if (!kn.fused_merge_off) bf.tickets = tickets;
     auto batch = [&]() {
         kt.begin(2, c->stream);
-        HIPCHK(launch_la_window(c->dt, dp, dx, 0, P, c->dc, geo, bf, on, ok, nullptr, nullptr, c->stream, 1));
+        HIPCHK(launch_la_window(c->dt, io.dp, io.dx, 0, P, c->dc, geo, bf, io.on, io.ok, nullptr, nullptr, c->stream, 1));
         kt.end(2, c->stream);
         kt.begin(3, c->stream);
-        HIPCHK(launch_batch_claim(c->dt, dp, bf.lists, ctrl, bidx, P, B, on, ok, c->stream));
+        HIPCHK(launch_batch_claim(c->dt, io.dp, bf.lists, ctrl, bidx, P, B, io.on, io.ok, c->stream));
         kt.end(3, c->stream);
     };
     const uint32_t nb0 = (P + B - 1) / B;
-    auto enqueue = [&]() {
+    // (the QS_SYNC_EVERY sync is not held back while capturing, unlike the lookahead's)
+    auto enqueue = [&](bool /*capturing*/) {
         HIPCHK(hipMemsetAsync(bf.lists, 0, 8 * lwords, c->stream));
         HIPCHK(hipMemsetAsync(tickets, 0, 4 * 64, c->stream));
         HIPCHK(launch_batch_init(ctrl, bidx, P, B, c->stream));
-        static const char *se = getenv("QS_SYNC_EVERY");  // profiling aid (see the lookahead run)
-        const uint32_t every = se ? (uint32_t)atoi(se) : 0u;
+        const uint32_t every = proc_knobs().sync_every;
         for (uint32_t b = 0; b < nb0; ++b) {
             batch();
             if (every && (b + 1) % every == 0 && !kt.on) HIPCHK(hipStreamSynchronize(c->stream));
         }
     };
-    static const char *genv = getenv("QS_GRAPH");
     // A stream of very many batches (small batch_pods: 100,000 batches of one pod) is enqueued directly:
     // its graph would be one chain of a few nodes per batch, and instantiating a chain of some 10^5
     // nodes ended the process with a segmentation fault (10,000 batches instantiate and replay fine)
     constexpr uint32_t kBatchGraphMax = 8192;
-    if (!kt.on && !(genv && genv[0] == '0') && nb0 <= kBatchGraphMax) {
-        std::vector<uint8_t> key;
-        auto put = [&](const void *p, size_t nb) { key.insert(key.end(), (const uint8_t *)p, (const uint8_t *)p + nb); };
-        const void *ptrs[] = {c->dt.rows, c->dt.wrows, c->dt.apps, bf.lists, bf.clists, ctrl, dp, on, ok};
-        put(ptrs, sizeof ptrs);
-        put(&c->dt.n, sizeof c->dt.n);
-        put(&c->dc, sizeof c->dc);
-        put(&geo, sizeof geo);
+    if (!kt.on && proc_knobs().graph != '0' && nb0 <= kBatchGraphMax) {
+        GraphKey key;
+        const void *ptrs[] = {c->dt.rows, c->dt.wrows, c->dt.apps, bf.lists, bf.clists, ctrl, io.dp, io.on, io.ok};
+        key_put(key, ptrs, sizeof ptrs);
+        key_put(key, &c->dt.n, sizeof c->dt.n);
+        key_put(key, &c->dc, sizeof c->dc);
+        key_put(key, &geo, sizeof geo);
         const int tag = 2;  // batched
-        put(&tag, sizeof tag);
-        put(&bf.tickets, sizeof bf.tickets);  // the merge form is read per run
-        if (!s->gexec || s->gkey != key) {
-            if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
-            s->gexec = nullptr;
-            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            try {
-                enqueue();
-            } catch (...) {
-                hipGraph_t g = nullptr;
-                (void)hipStreamEndCapture(c->stream, &g);
-                if (g) (void)hipGraphDestroy(g);
-                throw;
-            }
-            hipGraph_t g = nullptr;
-            HIPCHK(hipStreamEndCapture(c->stream, &g));
-            const hipError_t ie = hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            HIPCHK(ie);
-            s->gkey = key;
-        }
-        HIPCHK(hipGraphLaunch(s->gexec, c->stream));
+        key_put(key, &tag, sizeof tag);
+        key_put(key, &bf.tickets, sizeof bf.tickets);  // the merge form is read per run
+        replay_or_capture(c, s, key, enqueue);
     } else {
-        enqueue();
+        enqueue(false);
     }
     uint64_t batches = nb0;
     for (;;) {  // carried pods left after the planned batches
@@ -1056,6 +1159,638 @@ uint64_t run_batched(qs_ctx *c, qs_stream *s, const void *dp, const DPodX *dx, i
     c->soa_valid = false;
     return batches;
 }
+
+// SCAN: per pod one key scan (+ pre-pass) and one commit launch.  Returns the batch count (P).
+uint64_t run_scan(qs_ctx *c, const qs_stream *s, const RunIo &io, bool aa_exact, KernelTimer &kt) {
+    const uint32_t P = s->p;
+    HIPCHK(hipMemsetAsync(c->scratch.p, 0, scan_scratch_bytes(), c->stream));
+    ensure_soa(c);
+    for (uint32_t k = 0; k < P; k++) {
+        // (128: a soft-spread pod of a tracked stream, spec S14: the pre-pass in every class)
+        // (256: a hostname-spread pod, spec S15: the pre-pass for the minimum of its app's counts)
+        const int sp = !aa_exact ? 0 : s->soft[k] ? 128 : s->hosts[k] ? 256 : 0;
+        kt.begin(1, c->stream);  // the key scan alone (+ normalize pre-pass)
+        HIPCHK(launch_scan_pod(c->dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st,
+                               nullptr, nullptr, nullptr, 1 | sp, c->stream));
+        kt.end(1, c->stream);
+        HIPCHK(launch_scan_pod(c->dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st,
+                               nullptr, nullptr, nullptr, 2 | sp, c->stream));
+    }
+    return P;
+}
+
+// ALLREDUCE, SURVEY.md §8(e) C1 as-is: per pod every rank scans its contiguous node shard over the
+// rows, one ncclAllReduce(u64 max) of the packed key (C2: the two normalize maxima first), and every
+// rank applies the same Reserve to its replicated table.
+// virtual_shards = V > 1 on a one-rank communicator: this context scans all V node ranges of a V-rank
+// world in turn into the same scratch (the maxima with atomicMax, the keys max-into-best), so the
+// shard partition and the max over shards run exactly as V ranks would compute them (the test form of
+// the multi-rank engine).  Returns the batch count (P).
+uint64_t run_allreduce(qs_ctx *c, const qs_stream *s, const RunIo &io, KernelTimer &kt) {
+    const uint32_t n = c->m.n, P = s->p;
+    if (!c->comm)
+        fail(QS_ESTATE, "the all-reduce engine needs an RCCL communicator (qs_open_shard with an id)");
+    const uint32_t V = c->world == 1 && c->cfg.virtual_shards > 1 ? (uint32_t)c->cfg.virtual_shards : 1u;
+    const uint32_t R = V > 1 ? V : (uint32_t)c->world;
+    DevTable dt = c->dt;
+    std::memset(&dt.soa, 0, sizeof dt.soa);  // rows only (the SoA copy is marked stale after the run)
+    std::vector<uint32_t> sh(2 * (size_t)R);
+    for (uint32_t r = 0; r < R; ++r) {
+        sh[2 * r] = (uint32_t)((uint64_t)n * r / R);
+        sh[2 * r + 1] = (uint32_t)((uint64_t)n * (r + 1) / R);
+    }
+    const uint32_t r0 = V > 1 ? 0u : (uint32_t)c->rank;  // this rank's range (V = 1)
+    c->vshard.ensure(8 * (size_t)R);
+    HIPCHK(hipMemcpy(c->vshard.p, sh.data(), 8 * (size_t)R, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(c->scratch.p, 0, scan_scratch_bytes(), c->stream));
+    char *lohi = static_cast<char *>(c->scratch.p) + offsetof(ScanHead, lo);
+    auto range = [&](uint32_t r) {
+        return hipMemcpyAsync(lohi, c->vshard.as<uint32_t>() + 2 * r, 8, hipMemcpyDeviceToDevice, c->stream);
+    };
+    if (V == 1) HIPCHK(range(r0));
+    ScanHead *sc = c->scratch.as<ScanHead>();
+    const bool norm = (c->dc.feat & (kFeatTaint | kFeatAffinity)) != 0;
+    for (uint32_t k = 0; k < P; k++) {
+        kt.begin(1, c->stream);
+        if (norm) {
+            for (uint32_t v = 0; v < V; ++v) {
+                if (V > 1) HIPCHK(range(v));
+                HIPCHK(launch_scan_pod(dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st, nullptr,
+                                       nullptr, nullptr, 8, c->stream));
+            }
+            allreduce_max_u32(c, &sc->mt, 2, c->stream);
+        }
+        for (uint32_t v = 0; v < V; ++v) {
+            if (V > 1) HIPCHK(range(v));
+            HIPCHK(launch_scan_pod(dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st, nullptr,
+                                   nullptr, nullptr, 16 | 32, c->stream));
+        }
+        allreduce_max_u64(c, reinterpret_cast<uint64_t *>(&sc->best), 1, c->stream);
+        HIPCHK(launch_scan_pod(dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st, nullptr, nullptr,
+                               nullptr, 64, c->stream));
+        kt.end(1, c->stream);
+    }
+    return P;
+}
+
+// ---- LOOKAHEAD ---------------------------------------------------------------------------------
+// One lookahead run: what la_setup works out and every later step reads.
+struct LaRun {
+    RunIo io;
+    uint32_t n, P, nwin;
+    LaGeom geo;
+    size_t rank_entries;  // [K][GLp] list entries per shard
+    size_t lwords;        // one window's lists
+    size_t cwords;        // one window's chunk lists
+    size_t nparts;        // one window's partial maxima (uint4; normalizing profiles)
+    int nbuf;             // overlapped windows double-buffer the lists
+    bool norm;            // normalizing profile: k_la_norm pre-pass
+    bool overlap;         // select of window w+1 beside resolve of window w
+    bool mbox;            // sharded over the peer-memory mailbox (c->comm: RCCL)
+    bool handoff;         // per-window resolvers wait for their lists on a device word
+    uint64_t seq_run;     // tags the hand-off and mailbox words of this run (0: neither in use)
+    uint64_t *hw;         // the hand-off words {unused, ready, timeout flag}
+    uint64_t *diag;       // QS_DIAG stamps, else nullptr
+};
+
+// Geometry, the waves / key-width choice, the transport checks, the per-window buffers and the
+// hand-off words of a lookahead run.  `profiling`: config.profile_kernels brackets every launch.
+LaRun la_setup(qs_ctx *c, const qs_stream *s, const RunIo &io, const RunKnobs &kn, bool profiling) {
+    const ProcKnobs &pk = proc_knobs();
+    LaRun r{};
+    r.io = io;
+    r.n = c->m.n;
+    r.P = s->p;
+    r.overlap = la_overlap(c);
+    LaGeom &geo = r.geo;
+    geo = lookahead_geometry(c, r.n, r.overlap);
+    r.norm = (c->dc.feat & (kFeatTaint | kFeatAffinity)) != 0;
+    // sharded transport: RCCL (c->comm) or the peer-memory mailbox (c->mbox_on)
+    r.mbox = c->mbox_on && !c->comm;
+    if (c->world > 1 && !c->comm && !r.mbox)
+        fail(QS_ESTATE, "sharded context without a transport: pass an RCCL id to qs_open_shard "
+                        "or connect the mailbox (qs_dist_mailbox_connect)");
+    if (r.mbox && c->mbox_broken)
+        fail(QS_ESTATE, "mailbox ranks out of step after a timeout: every rank must call "
+                        "qs_dist_mailbox_connect again (between two barriers) before the next run");
+    // normalizing profiles: k_la_norm pre-pass + the single-wave k_la_resolve_norm
+    geo.waves = r.norm || (pk.resolver_waves1 && !r.overlap) ? 1u : 4u;
+    // normalizing profiles: the four-wave resolver with its stop/resume hand-off
+    // (overlapped windows, merged lists); QS_NORM_WAVES=1 keeps the single-wave kernel
+    if (r.norm && r.overlap && geo.epl == 1 && !kn.norm_waves1) geo.waves = 4;
+    int64_t wmax = 0;
+    for (int q = 0; q < 3; q++) wmax = std::max<int64_t>(wmax, (int64_t)c->cfg.w_fit[q] + c->cfg.w_bal[q]);
+    if (c->dc.feat & kFeatTaint) wmax += c->cfg.w_taint;       // every plugin scores <= 100
+    if (c->dc.feat & kFeatAffinity) wmax += c->cfg.w_affinity;
+    geo.k32 = (100 * wmax + 1 < 1024 && r.n <= (1u << 22)) ? 1u : 0u;
+    if (geo.G == 0) fail(QS_EINVAL, "no lookahead geometry for this table size");
+    r.rank_entries = (size_t)geo.K * 64 * geo.eplr;
+    r.lwords = geo.W * r.rank_entries;
+    r.cwords = std::max<size_t>(1, (size_t)geo.nv * geo.K * geo.G * geo.L);
+    r.nbuf = r.overlap ? 2 : 1;
+    c->lists.ensure(8 * r.lwords * r.nbuf);
+    c->clists.ensure(8 * r.cwords * r.nbuf);
+    c->dio.ensure(2 * kDioWords * 4);
+    r.nparts = r.norm ? (size_t)geo.W * geo.K * geo.G : 1;
+    c->npart.ensure(16 * r.nparts * r.nbuf);
+    c->normi.ensure(16 * (size_t)geo.K * r.nbuf);
+    c->nfall.ensure(16);
+    c->nrec.ensure(4 * kDioWords);
+    if (pk.diag) {
+        c->diag.ensure(128);
+        HIPCHK(hipMemsetAsync(c->diag.p, 0, 128, c->stream));
+        r.diag = c->diag.as<uint64_t>();
+    }
+    // in-kernel window hand-off (overlapped, unsharded windows): the resolver of window w
+    // waits for window w's lists on a device word instead of a cross-stream event, so
+    // consecutive resolver launches follow each other on one stream (QS_HANDOFF=0: events)
+    // Only for direct launches: under graph replay, dropping the per-window event edges
+    // let the executor serialise the select chain behind the resolvers (measured 122 vs
+    // 91 ms per config-2 stream), while direct launches on the two streams gain (88 ms).
+    // So overlapped unsharded runs launch directly with the hand-off by default
+    // (config 2: 1.147 M vs 1.075 M pods/s; config 4: 548 k vs 518 k); QS_GRAPH=1 forces
+    // graph replay (and events), QS_HANDOFF=0 keeps events.
+    // (not in profile_kernels runs: their per-launch events should bracket the
+    // resolver's own time, not an in-kernel wait)
+    const bool handoff_ok = r.overlap && !c->comm && !c->handoff_off && !profiling && !pk.handoff_off;
+    r.handoff = handoff_ok && pk.graph != '1';
+    if (!c->hand.p) {
+        c->hand.ensure(32);
+        HIPCHK(hipMemset(c->hand.p, 0, 32));
+    }
+    r.hw = c->hand.as<uint64_t>();
+    c->dc.ready = r.handoff ? r.hw + 1 : nullptr;
+    // the run's sequence number tags the hand-off and mailbox words (earlier runs compare
+    // lower; every rank of a sharded job runs the same streams, so the numbers agree)
+    r.seq_run = (r.handoff || r.mbox) ? ++c->run_seq : 0;
+    c->dc.epoch = r.handoff ? r.seq_run : 0;
+    c->last_waits = r.handoff || r.mbox;
+    if (r.mbox && (uint64_t)geo.K * geo.G > kMbPartPerRank)
+        fail(QS_EINVAL, "mailbox transport: K*G exceeds the mailbox partials capacity");
+    c->dc.werr = r.handoff ? reinterpret_cast<uint32_t *>(r.hw + 2) : nullptr;
+    r.nwin = (r.P + geo.K - 1) / geo.K;
+    return r;
+}
+
+// The buffers of window w: the lists' parity half when windows overlap, the mailbox slot when sharded
+// over it.
+LaBufs la_bufs(qs_ctx *c, const LaRun &r, uint32_t w) {
+    const int b = r.overlap ? (int)(w & 1) : 0;
+    uint32_t *dio = c->dio.as<uint32_t>();
+    LaBufs bf{c->lists.as<uint64_t>() + b * r.lwords, c->clists.as<uint64_t>() + b * r.cwords,
+              c->npart.as<uint4>() + b * r.nparts, c->normi.as<NormInfo>() + (size_t)b * r.geo.K, nullptr, nullptr,
+              c->nfall.as<unsigned long long>()};
+    bf.rec = c->nrec.as<uint32_t>();
+    if (r.mbox) {  // lists and partials live in this rank's mailbox, slot w % 3
+        bf.lists = mbox_lists(c, w % 3);
+        bf.npart = mbox_npart(c, w % 3);
+    }
+    if (r.overlap) {
+        bf.dprev = dio + ((w + 1) & 1) * kDioWords;
+        bf.dcur = dio + (w & 1) * kDioWords;
+    }
+    return bf;
+}
+
+// select (+ norm pre-pass, + merge, + the exchanges when sharded) of window w on stream `ss`
+void la_select(qs_ctx *c, const LaRun &r, KernelTimer &kt, uint32_t w, hipStream_t ss) {
+    const RunIo &io = r.io;
+    const LaGeom &geo = r.geo;
+    const LaBufs bf = la_bufs(c, r, w);
+    kt.begin(2, ss);
+    uint32_t *werr = reinterpret_cast<uint32_t *>(r.hw + 2);
+    if (r.norm) {
+        HIPCHK(launch_la_window(c->dt, io.dp, io.dx, w * geo.K, r.P, c->dc, geo, bf, io.on, io.ok, io.st, r.diag, ss, 4));
+        if (c->comm) exchange_u32(c, (uint32_t *)bf.npart, 4 * (size_t)geo.K * geo.G, ss);
+        else if (r.mbox) mbox_exchange(c, 0, w % 3, 16 * (size_t)geo.K * geo.G, 0, 0, (r.seq_run << 32) | (w + 1), werr, ss);
+    }
+    HIPCHK(launch_la_window(c->dt, io.dp, io.dx, w * geo.K, r.P, c->dc, geo, bf, io.on, io.ok, io.st, r.diag, ss, 1));
+    kt.end(2, ss);
+    if (c->comm) exchange_lists(c, bf.lists, r.rank_entries, ss);
+    else if (r.mbox) mbox_exchange(c, 1, w % 3, 8 * r.rank_entries, geo.K, geo.L, (r.seq_run << 32) | (w + 1), werr, ss);
+    if (r.handoff) HIPCHK(launch_ready_set(r.hw + 1, (c->dc.epoch << 32) | (w + 1), ss));
+}
+
+void la_resolve(qs_ctx *c, const LaRun &r, KernelTimer &kt, uint32_t w) {
+    const RunIo &io = r.io;
+    kt.begin(3, c->stream);
+    HIPCHK(launch_la_window(c->dt, io.dp, io.dx, w * r.geo.K, r.P, c->dc, r.geo, la_bufs(c, r, w), io.on, io.ok,
+                            io.st, r.diag, c->stream, 2));
+    kt.end(3, c->stream);
+}
+
+// The per-window launch sequence of the whole stream, issued directly or into a capture.
+void la_enqueue_windows(qs_ctx *c, const LaRun &r, KernelTimer &kt, bool capturing) {
+    // QS_SYNC_EVERY (individual launches only)
+    const uint32_t sync_every = capturing ? 0u : proc_knobs().sync_every;
+    // the run's timeout word: cleared before every run that waits on device words (the
+    // serial mailbox path too: a stale 1 would void every later run)
+    if (r.handoff || r.mbox) HIPCHK(hipMemsetAsync(r.hw + 2, 0, 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->lists.p, 0, 8 * r.lwords * r.nbuf, c->stream));  // padding stays 0
+    HIPCHK(hipMemsetAsync(c->dio.p, 0, 2 * kDioWords * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->nfall.p, 0, 16, c->stream));
+    if (!r.overlap) {
+        for (uint32_t w = 0; w < r.nwin; ++w) {
+            la_select(c, r, kt, w, c->stream);
+            la_resolve(c, r, kt, w);
+            if (sync_every && (w + 1) % sync_every == 0) HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        return;
+    }
+    // select(w+1) on the second stream runs beside resolve(w): it reads the table
+    // after resolve(w-1), so the resolver treats the nodes of window w as dirty too
+    // (lists of L = 2K keys).  Event rings order the two chains.
+    constexpr int R = 4;
+    hipEvent_t esel[R], eres[R], est;
+    for (int i = 0; i < R; ++i) {
+        HIPCHK(hipEventCreateWithFlags(&esel[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&eres[i], hipEventDisableTiming));
+    }
+    HIPCHK(hipEventCreateWithFlags(&est, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(est, c->stream));
+    HIPCHK(hipStreamWaitEvent(c->stream2, est, 0));
+    la_select(c, r, kt, 0, c->stream2);
+    HIPCHK(hipEventRecord(esel[0], c->stream2));
+    for (uint32_t w = 0; w < r.nwin; ++w) {
+        if (w + 1 < r.nwin) {
+            if (w >= 1) HIPCHK(hipStreamWaitEvent(c->stream2, eres[(w - 1) % R], 0));
+            la_select(c, r, kt, w + 1, c->stream2);
+            HIPCHK(hipEventRecord(esel[(w + 1) % R], c->stream2));
+        }
+        if (!r.handoff) HIPCHK(hipStreamWaitEvent(c->stream, esel[w % R], 0));
+        la_resolve(c, r, kt, w);
+        HIPCHK(hipEventRecord(eres[w % R], c->stream));
+        if (sync_every && (w + 1) % sync_every == 0) {
+            HIPCHK(hipStreamSynchronize(c->stream2));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+    }
+    hipEvent_t eend = nullptr;
+    if (r.handoff) {  // join the select stream (its last ready_set) back into the run
+        HIPCHK(hipEventCreateWithFlags(&eend, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(eend, c->stream2));
+        HIPCHK(hipStreamWaitEvent(c->stream, eend, 0));
+    }
+    for (int i = 0; i < R; ++i) {
+        (void)hipEventDestroy(esel[i]);
+        (void)hipEventDestroy(eres[i]);
+    }
+    (void)hipEventDestroy(est);
+    if (eend) (void)hipEventDestroy(eend);
+}
+
+// The key of the captured per-window sequence (replay_or_capture).
+GraphKey la_graph_key(const qs_ctx *c, const LaRun &r) {
+    GraphKey key;
+    const void *ptrs[] = {c->dt.rows, c->dt.wrows, c->dt.masks, c->lists.p, c->clists.p, c->dio.p, r.io.st,
+                          (void *)c->comm, r.io.dp, r.io.dx, c->npart.p, c->normi.p, c->nfall.p};
+    key_put(key, ptrs, sizeof ptrs);
+    key_put(key, &c->dt.n, sizeof c->dt.n);
+    key_put(key, &c->dc, sizeof c->dc);
+    key_put(key, &r.geo, sizeof r.geo);
+    key_put(key, &r.overlap, sizeof r.overlap);
+    return key;
+}
+
+// Resident stream: the whole overlapped window sequence of an unsharded Fit +
+// Balanced (+ extended) stream as ONE launch (resolver + selector workgroups handing off inside it);
+// QS_RESIDENT=0 keeps per-window launches.
+struct ResPlan {
+    LaGeom rgeo;    // the launch's geometry (G == 0: none fits)
+    uint32_t sel;   // selector workgroups
+    bool resident;  // the run is one resident launch
+};
+ResPlan la_plan_resident(qs_ctx *c, const LaRun &r, const RunKnobs &kn) {
+    const uint32_t feat = c->dc.feat, n = r.n;
+    if (!c->cus) {
+        int cu = 0;
+        HIPCHK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->cus = cu;
+    }
+    const uint32_t cus = (uint32_t)c->cus;
+    // two selector workgroups per CU when the occupancy check admits them, else one
+    // (normalizing profiles: the resident resolver is the four-wave one whatever the
+    // per-window geometry picked — sharded contexts keep the single-wave kernel there,
+    // epl > 1 — unless QS_NORM_WAVES=1 pins the single-wave path)
+    LaGeom pgeo = r.geo;
+    if (r.norm && r.overlap && !kn.norm_waves1) pgeo.waves = 4;
+    if (kn.res_k32_off) pgeo.k32 = 0;
+    ResPlan p{};
+    LaGeom &rgeo = p.rgeo;
+    rgeo = la_stream_res_plan(pgeo, feat, n, cus, 2);
+    if (rgeo.G > 0 && rgeo.K * rgeo.G + 1 > la_stream_res_max_blocks(rgeo, feat, n, cus))
+        rgeo = la_stream_res_plan(pgeo, feat, n, cus, 1);
+    // one selector workgroup per (pod, chunk) task of a window, at most one per
+    // remaining CU (they loop over the tasks otherwise); QS_RES_SEL overrides
+    p.sel = rgeo.K * rgeo.G;
+    if (proc_knobs().res_sel > 0) p.sel = proc_knobs().res_sel;
+    // normalizing profiles: the G chunk tasks of a pod wait for each other's partial
+    // maxima, so every task needs its own workgroup
+    if (r.norm) p.sel = std::max(p.sel, rgeo.K * rgeo.G);
+    // the launch's workgroups wait on each other: resident only when the occupancy
+    // query guarantees that all 1 + sel of them run at once (VERDICT r2 missing #5)
+    const bool coresident = rgeo.G > 0 && 1 + p.sel <= la_stream_res_max_blocks(rgeo, feat, n, cus);
+    // unsharded contexts, and mailbox-sharded ones for Fit + Balanced (+ extended)
+    // profiles: there the selectors exchange every pod's shard list through the peers'
+    // mailboxes inside the launch (RCCL cannot be called in a kernel)
+    const bool res_transport = c->world == 1 ? !r.mbox && !c->comm : r.mbox;
+    const bool res_allowed = c->res_timeouts < 2 && !c->res_cooldown;
+    p.resident = r.overlap && res_transport && res_allowed && !proc_knobs().diag && !kn.resident_off &&
+                 rgeo.G > 0 && coresident;
+    return p;
+}
+
+// Windows of identical pod records for the K a resident launch runs: the stream's bitmap on the
+// device (rebuilt when K changed), or nullptr when the launch takes none (QS_RES_UNIFORM=0, the
+// kernel class, no such window).  Sets s->uni_given.
+const uint32_t *la_uniform_windows(qs_ctx *c, qs_stream *s, const LaGeom &rgeo, uint32_t W, const RunKnobs &kn) {
+    const uint32_t P = s->p;
+    s->uni_given = 0;
+    if (kn.res_uniform_off || !la_stream_res_takes_uniform(rgeo, c->dc.feat, W) || s->run0.size() != P)
+        return nullptr;
+    if (s->uni_K != rgeo.K) {
+        const uint32_t K = rgeo.K, nwin = (P + K - 1) / K;
+        s->uni_bits.assign((nwin + 31) / 32 + 1, 0u);
+        s->uni_count = 0;
+        for (uint32_t w = 0; w < nwin; ++w) {
+            const uint32_t s0 = w * K, last = std::min(P, s0 + K) - 1;
+            if (s->run0[last] <= s0) {
+                s->uni_bits[w >> 5] |= 1u << (w & 31);
+                ++s->uni_count;
+            }
+        }
+        s->d_uni.ensure(4 * s->uni_bits.size());
+        HIPCHK(hipMemcpyAsync(s->d_uni.p, s->uni_bits.data(), 4 * s->uni_bits.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        s->uni_K = K;
+    }
+    if (!s->uni_count) return nullptr;
+    s->uni_given = s->uni_count;
+    return s->d_uni.as<uint32_t>();
+}
+
+// QS_RES_DIAG: the resident resolver's time split (list waits / window bodies / between), from the
+// launch's 128 diagnostic words.
+void la_report_res_diag(const uint64_t *h, uint32_t sel) {
+    const double nw = h[3] ? (double)h[3] : 1.0;
+    fprintf(stderr, "QS_RES_DIAG resolver %.3f us per window; windows whose lists were not prefetched %llu of %llu (selectors %u)\n",
+            h[1] * 0.01 / nw, (unsigned long long)h[4], (unsigned long long)h[3], sel);
+    if (h[2])
+        fprintf(stderr, "QS_RES_DIAG selector 0: done seen %.2f us, its task finished %.2f us after "
+                        "the resolver's start of the window it overlaps (%llu windows)\n",
+                h[13] * 0.01 / (double)h[2], h[14] * 0.01 / (double)h[2], (unsigned long long)h[2]);
+    {
+        std::vector<double> fin;
+        for (uint32_t k = 0; k < std::min(sel, 64u); ++k)
+            if (h[64 + k]) fin.push_back(h[64 + k] * 0.01);
+        std::sort(fin.begin(), fin.end());
+        if (!fin.empty()) {
+            fprintf(stderr, "QS_RES_DIAG selectors' mean finish (us after window start), sorted:");
+            for (double v : fin) fprintf(stderr, " %.1f", v);
+            fprintf(stderr, "\n");
+        }
+    }
+    if (h[36] + h[37] + h[38])
+        fprintf(stderr, "QS_RES_DIAG B3 -> B1 busy (ns per window, without the B1 wait): D %.0f, A %.0f, "
+                        "C %.0f\n", h[38] * 10.0 / nw, h[37] * 10.0 / nw, h[36] * 10.0 / nw);
+    if (h[41])
+        fprintf(stderr, "QS_RES_DIAG uniform windows %llu: %.2f us each from B1 to the window end, "
+                        "%.2f rounds each; the other windows %.2f us each, boundaries included\n",
+                (unsigned long long)h[41], h[40] * 0.01 / (double)h[41], (double)h[42] / (double)h[41],
+                h[3] > h[41] ? (h[1] - h[40]) * 0.01 / (double)(h[3] - h[41]) : 0.0);
+    if (h[33])
+        fprintf(stderr, "QS_RES_DIAG last list of a window published %.2f us after the start of "
+                        "the window before it (%llu windows; after 13 us %llu, after 15 us %llu)\n",
+                h[32] * 0.01 / (double)h[33], (unsigned long long)h[33],
+                (unsigned long long)h[34], (unsigned long long)h[35]);
+    if (h[6])
+        fprintf(stderr, "QS_RES_DIAG prefetch check: %llu windows short of lists, %.2f lists missing "
+                        "on average\n", (unsigned long long)h[6], (double)h[5] / (double)h[6]);
+    if (h[27] + h[28] + h[29] + h[30] + h[31])
+        fprintf(stderr, "QS_RES_DIAG window boundary (ns per window, wave D): bookkeeping %.0f "
+                        "-> B2 %.0f -> B3 %.0f -> B1 %.0f -> pod 0 decided %.0f\n",
+                h[27] * 10.0 / nw, h[28] * 10.0 / nw, h[29] * 10.0 / nw, h[30] * 10.0 / nw,
+                h[31] * 10.0 / nw);
+    if (h[19])
+        fprintf(stderr, "QS_RES_DIAG selector task (us): scoring %.2f chunk top-L %.2f publish/merge %.2f (tasks %llu, merges %llu)\n",
+                h[16] * 0.01 / (double)h[19], h[17] * 0.01 / (double)h[19], h[18] * 0.01 / (double)h[19],
+                (unsigned long long)h[19], (unsigned long long)h[20]);
+    if (h[12])  // QS_RES_DIAG_BLOCK build: busy shader cycles per pod step by role
+        fprintf(stderr, "QS_RES_DIAG busy cycles/step: D %.0f A %.0f B %.0f C %.0f (steps %llu)\n",
+                h[8] / (double)h[12], h[9] / (double)h[12], h[10] / (double)h[12],
+                h[11] / (double)h[12], (unsigned long long)h[12]);
+    if (h[12])
+        fprintf(stderr, "QS_RES_DIAG step marks: D argmax %.0f | A pub+reads %.0f applied %.0f | C reads %.0f keyC %.0f loads %.0f\n",
+                h[26] / (double)h[12], h[21] / (double)h[12], h[22] / (double)h[12],
+                h[23] / (double)h[12], h[24] / (double)h[12], h[25] / (double)h[12]);
+}
+
+// QS_DIAG: the per-window resolver's shader-clock stamps, from its 16 diagnostic words.
+void la_report_diag(const uint64_t *h, const LaGeom &geo, uint32_t nwin) {
+    const double np = h[5] ? (double)h[5] : 1.0;
+    fprintf(stderr, geo.waves == 1 ? "QS_DIAG resolve cycles/pod: cand %.0f issue %.0f fresh %.0f wmax %.0f commit %.0f (pods %llu, G=%u E=%u epl=%u)\n"
+                                   : "QS_DIAG resolve4 busy cycles/pod: D %.0f A %.0f B %.0f C %.0f (C row wait %.0f) (pods %llu, G=%u E=%u epl=%u)\n",
+            h[0] / np, h[1] / np, h[2] / np, h[3] / np, h[4] / np,
+            (unsigned long long)h[5], geo.G, geo.E, geo.epl);
+    if (geo.waves == 4)
+        fprintf(stderr, "QS_DIAG resolve4 pre-score cycles/pod: A %.0f C %.0f; per window: prologue %.0f epilogue %.0f\n",
+                h[6] / np, h[7] / np, h[8] / (double)nwin, h[9] / (double)nwin);
+}
+
+// The resident launch of the run `r` as `rp` plans it.
+void la_launch_resident(qs_ctx *c, qs_stream *s, const LaRun &r, const ResPlan &rp, const RunKnobs &kn,
+                        KernelTimer &kt) {
+    const RunIo &io = r.io;
+    const LaGeom &rgeo = rp.rgeo;
+    // what the resident geometry needs beyond la_setup's per-window sizes (DevBuf::ensure only grows, so
+    // each buffer ends at the larger of the two needs): its hand-off counters; per window parity the
+    // chunks' partial maxima and the pods' NormInfo of the normalizing profiles; the entry statics of the
+    // lists; its own chunk lists (its chunks differ from the per-window select's), double-buffered
+    const size_t rcw = std::max<size_t>(1, (size_t)rgeo.K * rgeo.G * rgeo.L);
+    c->resctl.ensure(la_stream_res_ctl_bytes());
+    c->npart.ensure(16 * 2 * (size_t)rgeo.K * rgeo.G);
+    c->normi.ensure(16 * 2 * 64);
+    c->nstat.ensure(4 * 2 * 128 * (size_t)rgeo.K);
+    c->clists.ensure(8 * rcw * 2);
+    // la_setup armed the per-window hand-off; the resident launch hands off inside the kernel: no ready
+    // word or epoch, but always the timeout word
+    c->dc.ready = nullptr;
+    c->dc.epoch = 0;
+    c->dc.werr = reinterpret_cast<uint32_t *>(r.hw + 2);
+    c->last_waits = true;
+    HIPCHK(hipMemsetAsync(c->lists.p, 0, 8 * r.lwords * r.nbuf, c->stream));  // padding stays 0
+    HIPCHK(hipMemsetAsync(c->dio.p, 0, 2 * kDioWords * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->resctl.p, 0, la_stream_res_ctl_bytes(), c->stream));
+    HIPCHK(hipMemsetAsync(r.hw + 2, 0, 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->nfall.p, 0, 16, c->stream));  // {rescans, windows with a rescan}
+    ResShard rsh{1u, 0u, 0ull, nullptr, 0ull, 0ull, 0ull, 0ull, 0ull};
+    if (c->world > 1)
+        rsh = ResShard{(uint32_t)c->world, (uint32_t)c->rank, r.seq_run, c->mbox_peers.as<char *>(),
+                       kMbResHello, kMbResFlags, kMbResLists, kMbResNFlags, kMbResNorm};
+    DevCfg dcr = c->dc;  // (the launch's copy: the test hooks never stick to the context)
+    // test hook: a selector that never delivers window 3 (one-shot), so the
+    // in-kernel timeout drain runs (tests/test_gpu_recovery.py)
+    // (QS_INJECT_FAULT=resident_stall_always: every resident launch of the context)
+    dcr.inject = (inject_once(c, kn.inject, "resident_stall", kInjResidentStall) ||
+                  (kn.inject && std::strcmp(kn.inject, "resident_stall_always") == 0)) ? 1u : 0u;
+    // (QS_INJECT_FAULT=resident_skew: this rank's selectors of windows 40-43 start 3 ms
+    // late, so the ranks of a sharded run drift apart in the middle of the stream)
+    if (kn.inject && std::strcmp(kn.inject, "resident_skew") == 0) dcr.inject = 2u;
+    // sharded: window 0's waits cover a peer still in host-side prepare (5 s)
+    dcr.first_ticks = c->world > 1 ? 500000000ull : 0ull;
+    // no node with allocatable cpu or memory 0: the key waves skip those terms
+    // (QS_FAST_ALLOC=0 keeps the generic scorers)
+    dcr.all_alloc = c->zero_alloc == 0 && !kn.fast_alloc_off ? 1u : 0u;
+    // what the launch runs (qs_stats::resident_path): the ring form carries 32-bit
+    // keys, and its two-resource classes read the flag
+    c->last_res_path = (!r.norm && rgeo.k32 ? 1 : 0) |
+                       (!r.norm && !(c->dc.feat & kFeatRes) && dcr.all_alloc ? 2 : 0);
+    dcr.sel_diag = kn.sel_diag ? 1u : 0u;
+    uint64_t *rdiag = nullptr;
+    if (proc_knobs().res_diag) {
+        c->diag.ensure(1024);
+        rdiag = c->diag.as<uint64_t>();
+        HIPCHK(hipMemsetAsync(rdiag, 0, 1024, c->stream));
+    }
+    const uint32_t *uni = la_uniform_windows(c, s, rgeo, rsh.W, kn);
+    kt.begin(3, c->stream);  // the one launch, under "resolve"
+    HIPCHK(launch_la_stream_res(c->dt, io.dp, io.dx, dcr, r.P, rgeo, c->lists.as<uint64_t>(), c->clists.as<uint64_t>(),
+                                (uint32_t)r.lwords, (uint32_t)rcw, c->npart.as<uint4>(),
+                                c->normi.as<NormInfo>(), c->nstat.as<uint32_t>(),
+                                c->nfall.as<unsigned long long>(), io.on, io.ok,
+                                io.st, c->resctl.p, rp.sel, rdiag, rsh, c->stream, uni));
+    kt.end(3, c->stream);
+    if (rdiag) {
+        uint64_t h[128] = {0};
+        HIPCHK(hipMemcpyAsync(h, rdiag, 1024, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        la_report_res_diag(h, rp.sel);
+    }
+}
+
+// LOOKAHEAD: windows of K pods, as one resident launch, a replayed graph of the per-window launches, or
+// those launches issued directly.  Returns the batch count (the windows).
+uint64_t run_lookahead(qs_ctx *c, qs_stream *s, const RunIo &io, const RunKnobs &kn, KernelTimer &kt) {
+    const ProcKnobs &pk = proc_knobs();
+    const LaRun r = la_setup(c, s, io, kn, kt.on);
+    const auto th0 = std::chrono::steady_clock::now();
+    // Replay the whole window sequence as one HIP graph (built on the first run of this
+    // prepared stream): ~3 launches + 4 event operations per window would otherwise
+    // be issued one host call at a time.  Not used for diagnostic runs.
+    // Multi-rank contexts enqueue directly: RCCL collectives inside a captured graph
+    // across ranks have not been observed on this pool yet; QS_GRAPH=1
+    // forces capture for them.
+    const bool graph_ok = !c->comm || pk.graph == '1';
+    const bool use_graph = graph_ok && !r.handoff && !r.mbox && !kt.on && !pk.diag && pk.graph != '0';
+    const ResPlan rp = la_plan_resident(c, r, kn);
+    c->last_resident = rp.resident;
+    // the per-window run after a resident timeout ends the cooldown (whatever it returns)
+    if (!rp.resident) c->res_cooldown = false;
+    if (rp.resident) {
+        la_launch_resident(c, s, r, rp, kn, kt);
+    } else if (use_graph) {
+        replay_or_capture(c, s, la_graph_key(c, r),
+                          [&](bool capturing) { la_enqueue_windows(c, r, kt, capturing); });
+    } else {
+        la_enqueue_windows(c, r, kt, false);
+    }
+    if (kn.hosttime)
+        fprintf(stderr, "QS_HOSTTIME enqueue %.3f ms for %u windows (overlap %d)\n",
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - th0).count() * 1e3,
+                r.nwin, (int)r.overlap);
+    if (pk.diag) {
+        uint64_t h[16] = {0};
+        HIPCHK(hipMemcpyAsync(h, r.diag, 128, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        la_report_diag(h, r.geo, r.nwin);
+    }
+    return r.nwin;
+}
+
+// After the run's device work has finished (`ms` between the driver's two events): the timeout word,
+// the mirror, the anti-affinity fold, the stream's validity and the stats.
+void finish_run(qs_ctx *c, qs_stream *s, qs_mode mode, const RunPlan &plan, const RunKnobs &kn, KernelTimer &kt,
+                uint64_t batches, float ms, qs_stats *stats) {
+    const uint32_t n = c->m.n, P = s->p;
+    const int eng = plan.eng;
+    uint64_t rescans = 0, resumed = 0;
+    if (eng == QS_ENGINE_LOOKAHEAD && c->last_waits) {
+        uint64_t w = 0;  // a resolver gave up waiting for its window's lists (device hand-off)
+        HIPCHK(hipMemcpy(&w, c->hand.as<uint64_t>() + 2, 8, hipMemcpyDeviceToHost));
+        if (inject_once(c, kn.inject, "handoff", kInjHandoff)) w = 1;  // test hook: a timed-out hand-off
+        if (w) {
+            // the select stream did not run beside the resolvers (e.g. a profiler serialising
+            // dispatches), or a mailbox peer never posted: the run's results and table updates
+            // are void and the device table is rebuilt from the host mirror (guarded(), as for
+            // a device fault); an unsharded context uses cross-stream events from now on
+            if (c->last_resident) {
+                ++c->res_timeouts;
+                c->res_cooldown = true;
+            } else if (!c->mbox_on) {
+                c->handoff_off = true;
+            }
+            if (c->mbox_on && !c->comm) c->mbox_broken = true;
+            fail(QS_ETIMEOUT, c->mbox_on ? "mailbox exchange timed out (a peer never posted its window)"
+                                         : c->last_resident
+                                               ? "resident lookahead stream timed out (a hand-off never arrived); "
+                                                 "the next run uses per-window launches"
+                                               : "lookahead window hand-off timed out (lists never published); "
+                                                 "the context falls back to stream events");
+        }
+    }
+    // a resident run that finished without a timeout: only CONSECUTIVE resident timeouts keep
+    // the context on per-window launches (qs_ctx.hpp)
+    if (eng == QS_ENGINE_LOOKAHEAD && c->last_resident) c->res_timeouts = 0;
+    if (eng == QS_ENGINE_LOOKAHEAD && c->nfall.p) {
+        uint64_t h[2] = {0, 0};
+        HIPCHK(hipMemcpy(h, c->nfall.p, 16, hipMemcpyDeviceToHost));
+        rescans = h[0];
+        resumed = h[1];
+        if (kn.norm_diag)
+            fprintf(stderr, "QS_NORM_DIAG rescans %llu resumed windows %llu\n", (unsigned long long)h[0],
+                    (unsigned long long)h[1]);
+    }
+    c->mirror_stale = true;
+    if (eng != QS_ENGINE_SCAN) c->soa_valid = false;  // those engines update the rows only
+    kt.finish();
+    maybe_inject_fault(c, kn.inject, "stream_run");
+    // keep the host mirror authoritative after every stream (one D2H of the rows, outside
+    // the timed region): a later device fault rebuilds the table from it
+    sync_mirror(c);
+    if (c->aa_track && P > 0 && n > 0) {
+        // fold the run's placements into the mirror's anti-affinity state (4 P bytes back, outside
+        // wall_s): the mirror stays authoritative for save / restore and the recovery rebuild
+        std::vector<int32_t> node(P);
+        HIPCHK(hipMemcpy(node.data(), s->d_node.p, 4 * (size_t)P, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < P; k++)
+            if (node[k] >= 0 && (uint32_t)node[k] < n)
+                c->m.aa_add((uint32_t)s->pods[s->order[k]].app, (uint32_t)node[k], +1);
+    }
+    s->aa_ran = plan.aa_exact;
+    s->ran = true;
+    s->mode_ran = (int)mode;
+    s->epoch_after = ++c->table_epoch;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        for (int k = 0; k < 4; k++) {
+            stats->kernel_s[k] = kt.secs[k];
+            stats->kernel_launches[k] = kt.count[k];
+        }
+        stats->pods = P;
+        stats->evals = (uint64_t)P * n;
+        stats->wall_s = ms * 1e-3;
+        stats->batches = batches;
+        stats->truncations = rescans;
+        stats->engine_used = eng;
+        stats->table_layout = c->wide ? 1 : 0;
+        stats->resumed_windows = resumed;
+        stats->resident = (eng == QS_ENGINE_LOOKAHEAD && c->last_resident) ? 1 : 0;
+        stats->resident_path = stats->resident ? c->last_res_path : 0;
+        stats->device_faults = c->device_faults;
+    }
+}
+
+}  // namespace
 
 // =============================================================================================
 // C ABI
@@ -1868,7 +2603,7 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         HIPCHK(hipSetDevice(c->device));
         // from here on the device table (and d_node) may change even if this run fails part way
         // (e.g. a resident timeout): invalidate the stream's results and every other stream's FitError
-        // replay now; only a successful run sets them again below
+        // replay now; only a successful run sets them again (finish_run)
         s->ran = false;
         s->mode_ran = -1;
         s->uni_given = 0;
@@ -1876,40 +2611,21 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         ++c->table_epoch;
         if (!c->dev_valid) upload_table(c);  // recovery after a device fault: rebuild from the mirror
         const uint32_t n = c->m.n, P = s->p;
-        c->dc.feat = s->feat;
-        // pod anti-affinity (spec S12): every exact stream of a tracking context carries the filter
-        // and records its pods; batched mode filters and records by itself (S11, the same state)
-        const bool aa_exact = c->aa_track && mode == QS_MODE_EXACT;
-        if (c->aa_track) aa_check_table(c);
-        if (aa_exact) {
-            c->dc.feat = aa_feat(s->feat);
-            // soft-spread pods (spec S14): the k_persistent instantiations that carry the score, and their caps
-            if (std::find(s->soft.begin(), s->soft.end(), 1) != s->soft.end()) c->dc.feat |= kFeatSoft;
-        }
-        // zone topology spread (spec S13): k_persistent keeps the counts of at most kSpreadApps apps
-        const bool spread_over = aa_exact && s->spread_apps > kSpreadApps;
-        // hostname topology spread (spec S15): the k_persistent instantiations that keep the (app, node)
-        // counts of the stream's hostname-spread apps in LDS (kFeatHost), for at most kHostSpreadApps apps
-        // and no soft pod in the same stream
-        const bool host_spread = aa_exact && s->host_pods != 0;
-        const bool has_soft = aa_exact && (c->dc.feat & kFeatSoft) != 0;
-        const bool host_over = host_spread && (s->host_apps > kHostSpreadApps || has_soft);
-        if (host_spread && !host_over) c->dc.feat |= kFeatHost;
-        const int eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, n, spread_over, host_over);
+        const RunKnobs kn;
+        const RunPlan plan = plan_run(c, s, mode);
         // the (app, node) counts: brought up to date for a stream that reads them; kept by the tracked
         // SCAN commit alone, so every other run that records pods on a tracking context leaves them stale
         // (k_persistent loads them at entry and keeps its own in LDS)
-        if (host_spread && n > 0) ensure_hcount(c);
-        if (c->aa_track && !(aa_exact && eng == QS_ENGINE_SCAN)) c->hc_valid = false;
-        if (host_spread && eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
+        if (plan.host_spread && n > 0) ensure_hcount(c);
+        if (c->aa_track && !(plan.aa_exact && plan.eng == QS_ENGINE_SCAN)) c->hc_valid = false;
+        if (plan.host_spread && plan.eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
             HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 4) * kMaxZones + 16, s->host_row,
                                   sizeof s->host_row, hipMemcpyHostToDevice, c->stream));
-        if (aa_exact && eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
+        if (plan.aa_exact && plan.eng == QS_ENGINE_PERSISTENT && n > 0 && P > 0)
             HIPCHK(hipMemcpyAsync(c->dt.zcount + (size_t)(kMaxApps + 1) * kMaxZones, s->spread_row,
                                   sizeof s->spread_row, hipMemcpyHostToDevice, c->stream));
-        int32_t *on = s->d_node.as<int32_t>();
-        uint64_t *ok = s->d_key.as<uint64_t>();
-        uint64_t *st = c->cfg.record_timestamps ? s->d_stamp.as<uint64_t>() : nullptr;
+        const RunIo io{s->d_pods.p, s->d_podx.as<DPodX>(), s->d_node.as<int32_t>(), s->d_key.as<uint64_t>(),
+                       c->cfg.record_timestamps ? s->d_stamp.as<uint64_t>() : nullptr};
         uint64_t batches = 0;
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0));
@@ -1918,516 +2634,20 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         KernelTimer kt(c->cfg.profile_kernels != 0, c->stream, c->stream2);
         HIPCHK(hipEventRecord(e0, c->stream));
         if (P > 0 && n == 0) {
-            HIPCHK(hipMemsetAsync(on, 0xFF, 4 * (size_t)P, c->stream));
-            HIPCHK(hipMemsetAsync(ok, 0, 8 * (size_t)P, c->stream));
+            HIPCHK(hipMemsetAsync(io.on, 0xFF, 4 * (size_t)P, c->stream));
+            HIPCHK(hipMemsetAsync(io.ok, 0, 8 * (size_t)P, c->stream));
         } else if (P > 0) {
-            const void *dp = s->d_pods.p;
-            const DPodX *dx = s->d_podx.as<DPodX>();
-            if (eng == QS_ENGINE_BATCHED) {
-                batches = run_batched(c, s, dp, dx, on, ok, kt);
-            } else if (eng == QS_ENGINE_PERSISTENT) {
+            switch (plan.eng) {
+            case QS_ENGINE_BATCHED: batches = run_batched(c, s, io, kn, kt); break;
+            case QS_ENGINE_PERSISTENT:
                 kt.begin(0, c->stream);
-                HIPCHK(launch_persistent(c->dt, dp, dx, P, c->dc, on, ok, st, c->stream));
+                HIPCHK(launch_persistent(c->dt, io.dp, io.dx, P, c->dc, io.on, io.ok, io.st, c->stream));
                 kt.end(0, c->stream);
                 batches = 1;
-            } else if (eng == QS_ENGINE_SCAN) {
-                HIPCHK(hipMemsetAsync(c->scratch.p, 0, scan_scratch_bytes(), c->stream));
-                ensure_soa(c);
-                for (uint32_t k = 0; k < P; k++) {
-                    // (128: a soft-spread pod of a tracked stream, spec S14: the pre-pass in every class)
-                    // (256: a hostname-spread pod, spec S15: the pre-pass for the minimum of its app's counts)
-                    const int sp = !aa_exact ? 0 : s->soft[k] ? 128 : s->hosts[k] ? 256 : 0;
-                    kt.begin(1, c->stream);  // the key scan alone (+ normalize pre-pass)
-                    HIPCHK(launch_scan_pod(c->dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st,
-                                           nullptr, nullptr, nullptr, 1 | sp, c->stream));
-                    kt.end(1, c->stream);
-                    HIPCHK(launch_scan_pod(c->dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st,
-                                           nullptr, nullptr, nullptr, 2 | sp, c->stream));
-                }
-                batches = P;
-            } else if (eng == QS_ENGINE_ALLREDUCE) {
-                // SURVEY.md §8(e) C1 as-is: per pod every rank scans its contiguous node shard over the
-                // rows, one ncclAllReduce(u64 max) of the packed key (C2: the two normalize maxima
-                // first), and every rank applies the same Reserve to its replicated table.
-                // virtual_shards = V > 1 on a one-rank communicator: this context scans all V node
-                // ranges of a V-rank world in turn into the same scratch (the maxima with atomicMax,
-                // the keys max-into-best), so the shard partition and the max over shards run
-                // exactly as V ranks would compute them (the test form of the multi-rank engine)
-                if (!c->comm)
-                    fail(QS_ESTATE, "the all-reduce engine needs an RCCL communicator (qs_open_shard with an id)");
-                const uint32_t V = c->world == 1 && c->cfg.virtual_shards > 1 ? (uint32_t)c->cfg.virtual_shards : 1u;
-                const uint32_t R = V > 1 ? V : (uint32_t)c->world;
-                DevTable dt = c->dt;
-                std::memset(&dt.soa, 0, sizeof dt.soa);  // rows only (the SoA copy is marked stale below)
-                std::vector<uint32_t> sh(2 * (size_t)R);
-                for (uint32_t r = 0; r < R; ++r) {
-                    sh[2 * r] = (uint32_t)((uint64_t)n * r / R);
-                    sh[2 * r + 1] = (uint32_t)((uint64_t)n * (r + 1) / R);
-                }
-                const uint32_t r0 = V > 1 ? 0u : (uint32_t)c->rank;  // this rank's range (V = 1)
-                c->vshard.ensure(8 * (size_t)R);
-                HIPCHK(hipMemcpy(c->vshard.p, sh.data(), 8 * (size_t)R, hipMemcpyHostToDevice));
-                HIPCHK(hipMemsetAsync(c->scratch.p, 0, scan_scratch_bytes(), c->stream));
-                char *lohi = static_cast<char *>(c->scratch.p) + offsetof(ScanHead, lo);
-                auto range = [&](uint32_t r) {
-                    return hipMemcpyAsync(lohi, c->vshard.as<uint32_t>() + 2 * r, 8, hipMemcpyDeviceToDevice, c->stream);
-                };
-                if (V == 1) HIPCHK(range(r0));
-                ScanHead *sc = c->scratch.as<ScanHead>();
-                const bool norm = (c->dc.feat & (kFeatTaint | kFeatAffinity)) != 0;
-                for (uint32_t k = 0; k < P; k++) {
-                    kt.begin(1, c->stream);
-                    if (norm) {
-                        for (uint32_t v = 0; v < V; ++v) {
-                            if (V > 1) HIPCHK(range(v));
-                            HIPCHK(launch_scan_pod(dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st, nullptr, nullptr,
-                                                   nullptr, 8, c->stream));
-                        }
-                        allreduce_max_u32(c, &sc->mt, 2, c->stream);
-                    }
-                    for (uint32_t v = 0; v < V; ++v) {
-                        if (V > 1) HIPCHK(range(v));
-                        HIPCHK(launch_scan_pod(dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st, nullptr, nullptr,
-                                               nullptr, 16 | 32, c->stream));
-                    }
-                    allreduce_max_u64(c, reinterpret_cast<uint64_t *>(&sc->best), 1, c->stream);
-                    HIPCHK(launch_scan_pod(dt, dp, dx, k, c->dc, c->scratch.p, on, ok, st, nullptr, nullptr,
-                                           nullptr, 64, c->stream));
-                    kt.end(1, c->stream);
-                }
-                batches = P;
-            } else {
-                const bool overlap = la_overlap(c);
-                LaGeom geo = lookahead_geometry(c, n, overlap);
-                static const char *rw = getenv("QS_RESOLVER_WAVES");  // 1 = single-wave resolver
-                const bool norm = (c->dc.feat & (kFeatTaint | kFeatAffinity)) != 0;
-                // sharded transport: RCCL (c->comm) or the peer-memory mailbox (c->mbox_on)
-                const bool mbox = c->mbox_on && !c->comm;
-                if (c->world > 1 && !c->comm && !mbox)
-                    fail(QS_ESTATE, "sharded context without a transport: pass an RCCL id to qs_open_shard "
-                                    "or connect the mailbox (qs_dist_mailbox_connect)");
-                if (mbox && c->mbox_broken)
-                    fail(QS_ESTATE, "mailbox ranks out of step after a timeout: every rank must call "
-                                    "qs_dist_mailbox_connect again (between two barriers) before the next run");
-                // normalizing profiles: k_la_norm pre-pass + the single-wave k_la_resolve_norm
-                geo.waves = norm || (rw && rw[0] == '1' && !overlap) ? 1u : 4u;
-                // normalizing profiles: the four-wave resolver with its stop/resume hand-off
-                // (overlapped windows, merged lists); QS_NORM_WAVES=1 keeps the single-wave kernel
-                const char *nw = getenv("QS_NORM_WAVES");  // read per run (tests pin it per case)
-                if (norm && overlap && geo.epl == 1 && !(nw && nw[0] == '1')) geo.waves = 4;
-                int64_t wmax = 0;
-                for (int q = 0; q < 3; q++) wmax = std::max<int64_t>(wmax, (int64_t)c->cfg.w_fit[q] + c->cfg.w_bal[q]);
-                if (c->dc.feat & kFeatTaint) wmax += c->cfg.w_taint;       // every plugin scores <= 100
-                if (c->dc.feat & kFeatAffinity) wmax += c->cfg.w_affinity;
-                geo.k32 = (100 * wmax + 1 < 1024 && n <= (1u << 22)) ? 1u : 0u;
-                if (geo.G == 0) fail(QS_EINVAL, "no lookahead geometry for this table size");
-                const size_t rank_entries = (size_t)geo.K * 64 * geo.eplr;  // [K][GLp] per shard
-                const size_t lwords = geo.W * rank_entries;                 // one window's lists
-                const size_t cwords = std::max<size_t>(1, (size_t)geo.nv * geo.K * geo.G * geo.L);
-                const int nbuf = overlap ? 2 : 1;  // overlapped windows double-buffer the lists
-                c->lists.ensure(8 * lwords * nbuf);
-                c->clists.ensure(8 * cwords * nbuf);
-                c->dio.ensure(2 * kDioWords * 4);
-                const size_t nparts = norm ? (size_t)geo.W * geo.K * geo.G : 1;  // uint4 per window
-                c->npart.ensure(16 * nparts * nbuf);
-                c->normi.ensure(16 * (size_t)geo.K * nbuf);
-                c->nfall.ensure(16);
-                c->nrec.ensure(4 * kDioWords);
-                // QS_DIAG=1: diagnostic resolver with per-segment shader-clock stamps (stderr)
-                static const bool diag_on = getenv("QS_DIAG") && getenv("QS_DIAG")[0] == '1';
-                uint64_t *diag = nullptr;
-                if (diag_on) {
-                    c->diag.ensure(128);
-                    HIPCHK(hipMemsetAsync(c->diag.p, 0, 128, c->stream));
-                    diag = c->diag.as<uint64_t>();
-                }
-                // in-kernel window hand-off (overlapped, unsharded windows): the resolver of window w
-                // waits for window w's lists on a device word instead of a cross-stream event, so
-                // consecutive resolver launches follow each other on one stream (QS_HANDOFF=0: events)
-                // Only for direct launches: under graph replay, dropping the per-window event edges
-                // let the executor serialise the select chain behind the resolvers (measured 122 vs
-                // 91 ms per config-2 stream), while direct launches on the two streams gain (88 ms).
-                // So overlapped unsharded runs launch directly with the hand-off by default
-                // (config 2: 1.147 M vs 1.075 M pods/s; config 4: 548 k vs 518 k); QS_GRAPH=1 forces
-                // graph replay (and events), QS_HANDOFF=0 keeps events.
-                static const char *ho = getenv("QS_HANDOFF");
-                static const char *genv0 = getenv("QS_GRAPH");
-                // (not in profile_kernels runs: their per-launch events should bracket the
-                // resolver's own time, not an in-kernel wait)
-                const bool handoff_ok = overlap && !c->comm && !c->handoff_off && !kt.on && !(ho && ho[0] == '0');
-                const bool graph_forced = genv0 && genv0[0] == '1';
-                const bool handoff = handoff_ok && !graph_forced;
-                if (!c->hand.p) {
-                    c->hand.ensure(32);
-                    HIPCHK(hipMemset(c->hand.p, 0, 32));
-                }
-                uint64_t *hw = c->hand.as<uint64_t>();
-                c->dc.ready = handoff ? hw + 1 : nullptr;
-                // the run's sequence number tags the hand-off and mailbox words (earlier runs compare
-                // lower; every rank of a sharded job runs the same streams, so the numbers agree)
-                const uint64_t seq_run = (handoff || mbox) ? ++c->run_seq : 0;
-                c->dc.epoch = handoff ? seq_run : 0;
-                c->last_waits = handoff || mbox;
-                if (mbox && (uint64_t)geo.K * geo.G > kMbPartPerRank)
-                    fail(QS_EINVAL, "mailbox transport: K*G exceeds the mailbox partials capacity");
-                c->dc.werr = handoff ? reinterpret_cast<uint32_t *>(hw + 2) : nullptr;
-                uint64_t *L0 = c->lists.as<uint64_t>(), *C0 = c->clists.as<uint64_t>();
-                uint32_t *dio = c->dio.as<uint32_t>();
-                const uint32_t nwin = (P + geo.K - 1) / geo.K;
-                const auto th0 = std::chrono::steady_clock::now();
-                // QS_SYNC_EVERY=n (profiling aid): bound the launches in flight under counter
-                // collection by a host sync every n windows (individual launches only)
-                static const char *se = getenv("QS_SYNC_EVERY");
-                const uint32_t sync_every = se ? (uint32_t)std::max(0, atoi(se)) : 0u;
-                bool capturing = false;
-                auto enqueue = [&]() {
-                // the run's timeout word: cleared before every run that waits on device words (the
-                // serial mailbox path too: a stale 1 would void every later run)
-                if (handoff || mbox) HIPCHK(hipMemsetAsync(hw + 2, 0, 8, c->stream));
-                HIPCHK(hipMemsetAsync(c->lists.p, 0, 8 * lwords * nbuf, c->stream));  // padding stays 0
-                HIPCHK(hipMemsetAsync(c->dio.p, 0, 2 * kDioWords * 4, c->stream));
-                HIPCHK(hipMemsetAsync(c->nfall.p, 0, 16, c->stream));
-                auto bufs = [&](uint32_t w) {
-                    const int b = overlap ? (int)(w & 1) : 0;
-                    LaBufs bf{L0 + b * lwords, C0 + b * cwords, c->npart.as<uint4>() + b * nparts,
-                              c->normi.as<NormInfo>() + (size_t)b * geo.K, nullptr, nullptr,
-                              c->nfall.as<unsigned long long>()};
-                    bf.rec = c->nrec.as<uint32_t>();
-                    if (mbox) {  // lists and partials live in this rank's mailbox, slot w % 3
-                        bf.lists = mbox_lists(c, w % 3);
-                        bf.npart = mbox_npart(c, w % 3);
-                    }
-                    if (overlap) {
-                        bf.dprev = dio + ((w + 1) & 1) * kDioWords;
-                        bf.dcur = dio + (w & 1) * kDioWords;
-                    }
-                    return bf;
-                };
-                // select (+ norm pre-pass, + merge, + the RCCL exchanges when sharded) of window w
-                // on stream `ss`
-                auto select = [&](uint32_t w, hipStream_t ss) {
-                    const LaBufs bf = bufs(w);
-                    kt.begin(2, ss);
-                    uint32_t *werr = reinterpret_cast<uint32_t *>(hw + 2);
-                    if (norm) {
-                        HIPCHK(launch_la_window(c->dt, dp, dx, w * geo.K, P, c->dc, geo, bf, on, ok, st, diag, ss, 4));
-                        if (c->comm) exchange_u32(c, (uint32_t *)bf.npart, 4 * (size_t)geo.K * geo.G, ss);
-                        else if (mbox) mbox_exchange(c, 0, w % 3, 16 * (size_t)geo.K * geo.G, 0, 0, (seq_run << 32) | (w + 1), werr, ss);
-                    }
-                    HIPCHK(launch_la_window(c->dt, dp, dx, w * geo.K, P, c->dc, geo, bf, on, ok, st, diag, ss, 1));
-                    kt.end(2, ss);
-                    if (c->comm) exchange_lists(c, bf.lists, rank_entries, ss);
-                    else if (mbox) mbox_exchange(c, 1, w % 3, 8 * rank_entries, geo.K, geo.L, (seq_run << 32) | (w + 1), werr, ss);
-                    if (handoff) HIPCHK(launch_ready_set(hw + 1, (c->dc.epoch << 32) | (w + 1), ss));
-                };
-                auto resolve = [&](uint32_t w) {
-                    kt.begin(3, c->stream);
-                    HIPCHK(launch_la_window(c->dt, dp, dx, w * geo.K, P, c->dc, geo, bufs(w), on, ok, st,
-                                            diag, c->stream, 2));
-                    kt.end(3, c->stream);
-                };
-                if (!overlap) {
-                    for (uint32_t w = 0; w < nwin; ++w) {
-                        select(w, c->stream);
-                        resolve(w);
-                        if (sync_every && !capturing && (w + 1) % sync_every == 0)
-                            HIPCHK(hipStreamSynchronize(c->stream));
-                    }
-                } else {
-                    // select(w+1) on the second stream runs beside resolve(w): it reads the table
-                    // after resolve(w-1), so the resolver treats the nodes of window w as dirty too
-                    // (lists of L = 2K keys).  Event rings order the two chains.
-                    constexpr int R = 4;
-                    hipEvent_t esel[R], eres[R], est;
-                    for (int r = 0; r < R; ++r) {
-                        HIPCHK(hipEventCreateWithFlags(&esel[r], hipEventDisableTiming));
-                        HIPCHK(hipEventCreateWithFlags(&eres[r], hipEventDisableTiming));
-                    }
-                    HIPCHK(hipEventCreateWithFlags(&est, hipEventDisableTiming));
-                    HIPCHK(hipEventRecord(est, c->stream));
-                    HIPCHK(hipStreamWaitEvent(c->stream2, est, 0));
-                    select(0, c->stream2);
-                    HIPCHK(hipEventRecord(esel[0], c->stream2));
-                    for (uint32_t w = 0; w < nwin; ++w) {
-                        if (w + 1 < nwin) {
-                            if (w >= 1) HIPCHK(hipStreamWaitEvent(c->stream2, eres[(w - 1) % R], 0));
-                            select(w + 1, c->stream2);
-                            HIPCHK(hipEventRecord(esel[(w + 1) % R], c->stream2));
-                        }
-                        if (!handoff) HIPCHK(hipStreamWaitEvent(c->stream, esel[w % R], 0));
-                        resolve(w);
-                        HIPCHK(hipEventRecord(eres[w % R], c->stream));
-                        if (sync_every && !capturing && (w + 1) % sync_every == 0) {
-                            HIPCHK(hipStreamSynchronize(c->stream2));
-                            HIPCHK(hipStreamSynchronize(c->stream));
-                        }
-                    }
-                    hipEvent_t eend = nullptr;
-                    if (handoff) {  // join the select stream (its last ready_set) back into the run
-                        HIPCHK(hipEventCreateWithFlags(&eend, hipEventDisableTiming));
-                        HIPCHK(hipEventRecord(eend, c->stream2));
-                        HIPCHK(hipStreamWaitEvent(c->stream, eend, 0));
-                    }
-                    for (int r = 0; r < R; ++r) {
-                        (void)hipEventDestroy(esel[r]);
-                        (void)hipEventDestroy(eres[r]);
-                    }
-                    (void)hipEventDestroy(est);
-                    if (eend) (void)hipEventDestroy(eend);
-                }
-                };
-                // Replay the whole window sequence as one HIP graph (built on the first run of this
-                // prepared stream): ~3 launches + 4 event operations per window would otherwise
-                // be issued one host call at a time.  Not used for diagnostic runs.
-                static const char *genv = getenv("QS_GRAPH");
-                // Multi-rank contexts enqueue directly: RCCL collectives inside a captured graph
-                // across ranks have not been observed on this pool yet; QS_GRAPH=1
-                // forces capture for them.
-                const bool graph_ok = !c->comm || (genv && genv[0] == '1');
-                const bool use_graph = graph_ok && !handoff && !mbox && !kt.on && !diag_on && !(genv && genv[0] == '0');
-                // Resident stream: the whole overlapped window sequence of an
-                // unsharded Fit + Balanced (+ extended) stream as ONE launch (resolver + selector
-                // workgroups handing off inside it); QS_RESIDENT=0 keeps per-window launches.
-                const char *renv = getenv("QS_RESIDENT");  // read per run (tests switch it per case)
-                if (!c->cus) {
-                    int cu = 0;
-                    HIPCHK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device));
-                    c->cus = cu;
-                }
-                // two selector workgroups per CU when the occupancy check admits them, else one
-                // (normalizing profiles: the resident resolver is the four-wave one whatever the
-                // per-window geometry picked — sharded contexts keep the single-wave kernel there,
-                // epl > 1 — unless QS_NORM_WAVES=1 pins the single-wave path)
-                LaGeom pgeo = geo;
-                if (norm && overlap && !(nw && nw[0] == '1')) pgeo.waves = 4;
-                // QS_RES_K32=0: the resident resolver's 64-bit key path (read per run: tests and
-                // A/B timing run both widths from one library)
-                const char *rk = getenv("QS_RES_K32");
-                if (rk && rk[0] == '0') pgeo.k32 = 0;
-                LaGeom rgeo = la_stream_res_plan(pgeo, c->dc.feat, n, (uint32_t)c->cus, 2);
-                if (rgeo.G > 0 && rgeo.K * rgeo.G + 1 > la_stream_res_max_blocks(rgeo, c->dc.feat, n, (uint32_t)c->cus))
-                    rgeo = la_stream_res_plan(pgeo, c->dc.feat, n, (uint32_t)c->cus, 1);
-                // one selector workgroup per (pod, chunk) task of a window, at most one per
-                // remaining CU (they loop over the tasks otherwise); QS_RES_SEL overrides
-                static const char *senv = getenv("QS_RES_SEL");
-                uint32_t sel = rgeo.K * rgeo.G;
-                if (senv && atoi(senv) > 0) sel = (uint32_t)atoi(senv);
-                // normalizing profiles: the G chunk tasks of a pod wait for each other's partial
-                // maxima, so every task needs its own workgroup
-                if (norm) sel = std::max(sel, rgeo.K * rgeo.G);
-                // the launch's workgroups wait on each other: resident only when the occupancy
-                // query guarantees that all 1 + sel of them run at once (VERDICT r2 missing #5)
-                const bool coresident =
-                    rgeo.G > 0 && 1 + sel <= la_stream_res_max_blocks(rgeo, c->dc.feat, n, (uint32_t)c->cus);
-                // unsharded contexts, and mailbox-sharded ones for Fit + Balanced (+ extended)
-                // profiles: there the selectors exchange every pod's shard list through the peers'
-                // mailboxes inside the launch (RCCL cannot be called in a kernel)
-                const bool res_transport = c->world == 1 ? !mbox && !c->comm : mbox;
-                const bool res_allowed = c->res_timeouts < 2 && !c->res_cooldown;
-                const bool resident = overlap && res_transport && res_allowed && !diag_on &&
-                                      !(renv && renv[0] == '0') && rgeo.G > 0 && coresident;
-                c->last_resident = resident;
-                // the per-window run after a resident timeout ends the cooldown (whatever it returns)
-                if (!resident) c->res_cooldown = false;
-                if (resident) {
-                    c->resctl.ensure(la_stream_res_ctl_bytes());
-                    c->dc.ready = nullptr;
-                    c->dc.epoch = 0;
-                    c->dc.werr = reinterpret_cast<uint32_t *>(hw + 2);
-                    c->last_waits = true;
-                    HIPCHK(hipMemsetAsync(c->lists.p, 0, 8 * lwords * nbuf, c->stream));  // padding stays 0
-                    HIPCHK(hipMemsetAsync(c->dio.p, 0, 2 * kDioWords * 4, c->stream));
-                    HIPCHK(hipMemsetAsync(c->resctl.p, 0, la_stream_res_ctl_bytes(), c->stream));
-                    HIPCHK(hipMemsetAsync(hw + 2, 0, 8, c->stream));
-                    // normalizing profiles: per window parity the chunks' partial maxima and the
-                    // pods' NormInfo; {rescans, windows with a rescan}
-                    c->npart.ensure(16 * 2 * (size_t)rgeo.K * rgeo.G);
-                    c->normi.ensure(16 * 2 * 64);
-                    c->nstat.ensure(4 * 2 * 128 * (size_t)rgeo.K);  // entry statics of the lists
-                    HIPCHK(hipMemsetAsync(c->nfall.p, 0, 16, c->stream));
-                    // chunk lists of the resident geometry (its chunks differ from the per-window
-                    // select's), double-buffered by window parity
-                    const size_t rcw = std::max<size_t>(1, (size_t)rgeo.K * rgeo.G * rgeo.L);
-                    c->clists.ensure(8 * rcw * 2);
-                    ResShard rsh{1u, 0u, 0ull, nullptr, 0ull, 0ull, 0ull, 0ull, 0ull};
-                    if (c->world > 1)
-                        rsh = ResShard{(uint32_t)c->world, (uint32_t)c->rank, seq_run, c->mbox_peers.as<char *>(),
-                                       kMbResHello, kMbResFlags, kMbResLists, kMbResNFlags, kMbResNorm};
-                    // test hook: a selector that never delivers window 3 (one-shot), so the
-                    // in-kernel timeout drain runs (tests/test_gpu_recovery.py)
-                    DevCfg dcr = c->dc;  // (the launch's copy: the hook never sticks to the context)
-                    // (QS_INJECT_FAULT=resident_stall_always: every resident launch of the context)
-                    const char *inj = getenv("QS_INJECT_FAULT");
-                    dcr.inject = (inject_once(c, "resident_stall", kInjResidentStall) ||
-                                  (inj && std::strcmp(inj, "resident_stall_always") == 0)) ? 1u : 0u;
-                    // (QS_INJECT_FAULT=resident_skew: this rank's selectors of windows 40-43 start 3 ms
-                    // late, so the ranks of a sharded run drift apart in the middle of the stream)
-                    if (inj && std::strcmp(inj, "resident_skew") == 0) dcr.inject = 2u;
-                    // sharded: window 0's waits cover a peer still in host-side prepare (5 s)
-                    dcr.first_ticks = c->world > 1 ? 500000000ull : 0ull;
-                    // no node with allocatable cpu or memory 0: the key waves skip those terms
-                    // (QS_FAST_ALLOC=0 keeps the generic scorers; read per run, tests switch it)
-                    const char *fa = getenv("QS_FAST_ALLOC");
-                    dcr.all_alloc = c->zero_alloc == 0 && !(fa && fa[0] == '0') ? 1u : 0u;
-                    // what the launch runs (qs_stats::resident_path): the ring form carries 32-bit
-                    // keys, and its two-resource classes read the flag
-                    c->last_res_path = (!norm && rgeo.k32 ? 1 : 0) |
-                                       (!norm && !(c->dc.feat & kFeatRes) && dcr.all_alloc ? 2 : 0);
-                    // QS_RES_DIAG=1: the resolver's time split (list waits / window bodies / between)
-                    static const bool rdiag_on = getenv("QS_RES_DIAG") && (getenv("QS_RES_DIAG")[0] == '1' ||
-                                                                             getenv("QS_RES_DIAG")[0] == '2');
-                    dcr.sel_diag = getenv("QS_RES_DIAG") && getenv("QS_RES_DIAG")[0] == '1' ? 1u : 0u;
-                    uint64_t *rdiag = nullptr;
-                    if (rdiag_on) {
-                        c->diag.ensure(1024);
-                        rdiag = c->diag.as<uint64_t>();
-                        HIPCHK(hipMemsetAsync(rdiag, 0, 1024, c->stream));
-                    }
-                    // windows of identical pod records, for the K this launch runs (QS_RES_UNIFORM=0:
-                    // none, read per run: tests and A/B timing run both paths from one library)
-                    const char *ue = getenv("QS_RES_UNIFORM");
-                    const uint32_t *uni = nullptr;
-                    s->uni_given = 0;
-                    if (!(ue && ue[0] == '0') && la_stream_res_takes_uniform(rgeo, c->dc.feat, rsh.W) &&
-                        s->run0.size() == P) {
-                        if (s->uni_K != rgeo.K) {
-                            const uint32_t K = rgeo.K, nwin = (P + K - 1) / K;
-                            s->uni_bits.assign((nwin + 31) / 32 + 1, 0u);
-                            s->uni_count = 0;
-                            for (uint32_t w = 0; w < nwin; ++w) {
-                                const uint32_t s0 = w * K, last = std::min(P, s0 + K) - 1;
-                                if (s->run0[last] <= s0) {
-                                    s->uni_bits[w >> 5] |= 1u << (w & 31);
-                                    ++s->uni_count;
-                                }
-                            }
-                            s->d_uni.ensure(4 * s->uni_bits.size());
-                            HIPCHK(hipMemcpyAsync(s->d_uni.p, s->uni_bits.data(), 4 * s->uni_bits.size(),
-                                                  hipMemcpyHostToDevice, c->stream));
-                            s->uni_K = K;
-                        }
-                        if (s->uni_count) {
-                            uni = s->d_uni.as<uint32_t>();
-                            s->uni_given = s->uni_count;
-                        }
-                    }
-                    kt.begin(3, c->stream);  // the one launch, under "resolve"
-                    HIPCHK(launch_la_stream_res(c->dt, dp, dx, dcr, P, rgeo, L0, c->clists.as<uint64_t>(),
-                                                (uint32_t)lwords, (uint32_t)rcw, c->npart.as<uint4>(),
-                                                c->normi.as<NormInfo>(), c->nstat.as<uint32_t>(),
-                                                c->nfall.as<unsigned long long>(), on, ok,
-                                                st, c->resctl.p, sel, rdiag, rsh, c->stream, uni));
-                    kt.end(3, c->stream);
-                    if (rdiag) {
-                        uint64_t h[128] = {0};
-                        HIPCHK(hipMemcpyAsync(h, rdiag, 1024, hipMemcpyDeviceToHost, c->stream));
-                        HIPCHK(hipStreamSynchronize(c->stream));
-                        const double nw = h[3] ? (double)h[3] : 1.0;
-                        fprintf(stderr, "QS_RES_DIAG resolver %.3f us per window; windows whose lists were not prefetched %llu of %llu (selectors %u)\n",
-                                h[1] * 0.01 / nw, (unsigned long long)h[4], (unsigned long long)h[3], sel);
-                        if (h[2])
-                            fprintf(stderr, "QS_RES_DIAG selector 0: done seen %.2f us, its task finished %.2f us after "
-                                            "the resolver's start of the window it overlaps (%llu windows)\n",
-                                    h[13] * 0.01 / (double)h[2], h[14] * 0.01 / (double)h[2], (unsigned long long)h[2]);
-                        {
-                            std::vector<double> fin;
-                            for (uint32_t k = 0; k < std::min(sel, 64u); ++k)
-                                if (h[64 + k]) fin.push_back(h[64 + k] * 0.01);
-                            std::sort(fin.begin(), fin.end());
-                            if (!fin.empty()) {
-                                fprintf(stderr, "QS_RES_DIAG selectors' mean finish (us after window start), sorted:");
-                                for (double v : fin) fprintf(stderr, " %.1f", v);
-                                fprintf(stderr, "\n");
-                            }
-                        }
-                        if (h[36] + h[37] + h[38])
-                            fprintf(stderr, "QS_RES_DIAG B3 -> B1 busy (ns per window, without the B1 wait): D %.0f, A %.0f, "
-                                            "C %.0f\n", h[38] * 10.0 / nw, h[37] * 10.0 / nw, h[36] * 10.0 / nw);
-                        if (h[41])
-                            fprintf(stderr, "QS_RES_DIAG uniform windows %llu: %.2f us each from B1 to the window end, "
-                                            "%.2f rounds each; the other windows %.2f us each, boundaries included\n",
-                                    (unsigned long long)h[41], h[40] * 0.01 / (double)h[41], (double)h[42] / (double)h[41],
-                                    h[3] > h[41] ? (h[1] - h[40]) * 0.01 / (double)(h[3] - h[41]) : 0.0);
-                        if (h[33])
-                            fprintf(stderr, "QS_RES_DIAG last list of a window published %.2f us after the start of "
-                                            "the window before it (%llu windows; after 13 us %llu, after 15 us %llu)\n",
-                                    h[32] * 0.01 / (double)h[33], (unsigned long long)h[33],
-                                    (unsigned long long)h[34], (unsigned long long)h[35]);
-                        if (h[6])
-                            fprintf(stderr, "QS_RES_DIAG prefetch check: %llu windows short of lists, %.2f lists missing "
-                                            "on average\n", (unsigned long long)h[6], (double)h[5] / (double)h[6]);
-                        if (h[27] + h[28] + h[29] + h[30] + h[31])
-                            fprintf(stderr, "QS_RES_DIAG window boundary (ns per window, wave D): bookkeeping %.0f "
-                                            "-> B2 %.0f -> B3 %.0f -> B1 %.0f -> pod 0 decided %.0f\n",
-                                    h[27] * 10.0 / nw, h[28] * 10.0 / nw, h[29] * 10.0 / nw, h[30] * 10.0 / nw,
-                                    h[31] * 10.0 / nw);
-                        if (h[19])
-                            fprintf(stderr, "QS_RES_DIAG selector task (us): scoring %.2f chunk top-L %.2f publish/merge %.2f (tasks %llu, merges %llu)\n",
-                                    h[16] * 0.01 / (double)h[19], h[17] * 0.01 / (double)h[19], h[18] * 0.01 / (double)h[19],
-                                    (unsigned long long)h[19], (unsigned long long)h[20]);
-                        if (h[12])  // QS_RES_DIAG_BLOCK build: busy shader cycles per pod step by role
-                            fprintf(stderr, "QS_RES_DIAG busy cycles/step: D %.0f A %.0f B %.0f C %.0f (steps %llu)\n",
-                                    h[8] / (double)h[12], h[9] / (double)h[12], h[10] / (double)h[12],
-                                    h[11] / (double)h[12], (unsigned long long)h[12]);
-                        if (h[12])
-                            fprintf(stderr, "QS_RES_DIAG step marks: D argmax %.0f | A pub+reads %.0f applied %.0f | C reads %.0f keyC %.0f loads %.0f\n",
-                                    h[26] / (double)h[12], h[21] / (double)h[12], h[22] / (double)h[12],
-                                    h[23] / (double)h[12], h[24] / (double)h[12], h[25] / (double)h[12]);
-                    }
-                } else if (use_graph) {
-                    std::vector<uint8_t> key;
-                    auto put = [&](const void *p, size_t nb) {
-                        key.insert(key.end(), (const uint8_t *)p, (const uint8_t *)p + nb);
-                    };
-                    const void *ptrs[] = {c->dt.rows, c->dt.wrows, c->dt.masks, L0, C0, dio, st, (void *)c->comm, dp, dx,
-                                          c->npart.p, c->normi.p, c->nfall.p};
-                    put(ptrs, sizeof ptrs);
-                    put(&c->dt.n, sizeof c->dt.n);
-                    put(&c->dc, sizeof c->dc);
-                    put(&geo, sizeof geo);
-                    put(&overlap, sizeof overlap);
-                    if (!s->gexec || s->gkey != key) {
-                        if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
-                        s->gexec = nullptr;
-                        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                        capturing = true;
-                        try {
-                            enqueue();
-                        } catch (...) {
-                            hipGraph_t g = nullptr;
-                            (void)hipStreamEndCapture(c->stream, &g);
-                            if (g) (void)hipGraphDestroy(g);
-                            throw;
-                        }
-                        hipGraph_t g = nullptr;
-                        HIPCHK(hipStreamEndCapture(c->stream, &g));
-                        const hipError_t ie = hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0);
-                        (void)hipGraphDestroy(g);
-                        HIPCHK(ie);
-                        s->gkey = key;
-                    }
-                    HIPCHK(hipGraphLaunch(s->gexec, c->stream));
-                } else {
-                    enqueue();
-                }
-                batches = nwin;
-                if (getenv("QS_HOSTTIME"))
-                    fprintf(stderr, "QS_HOSTTIME enqueue %.3f ms for %u windows (overlap %d)\n",
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - th0).count() * 1e3,
-                            nwin, (int)overlap);
-                if (diag_on) {
-                    uint64_t h[16] = {0};
-                    HIPCHK(hipMemcpyAsync(h, diag, 128, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                    const double np = h[5] ? (double)h[5] : 1.0;
-                    fprintf(stderr, geo.waves == 1 ? "QS_DIAG resolve cycles/pod: cand %.0f issue %.0f fresh %.0f wmax %.0f commit %.0f (pods %llu, G=%u E=%u epl=%u)\n"
-                                                   : "QS_DIAG resolve4 busy cycles/pod: D %.0f A %.0f B %.0f C %.0f (C row wait %.0f) (pods %llu, G=%u E=%u epl=%u)\n",
-                            h[0] / np, h[1] / np, h[2] / np, h[3] / np, h[4] / np,
-                            (unsigned long long)h[5], geo.G, geo.E, geo.epl);
-                    if (geo.waves == 4)
-                        fprintf(stderr, "QS_DIAG resolve4 pre-score cycles/pod: A %.0f C %.0f; per window: prologue %.0f epilogue %.0f\n",
-                                h[6] / np, h[7] / np, h[8] / (double)nwin, h[9] / (double)nwin);
-                }
+                break;
+            case QS_ENGINE_SCAN: batches = run_scan(c, s, io, plan.aa_exact, kt); break;
+            case QS_ENGINE_ALLREDUCE: batches = run_allreduce(c, s, io, kt); break;
+            default: batches = run_lookahead(c, s, io, kn, kt); break;
             }
         }
         HIPCHK(hipEventRecord(e1, c->stream));
@@ -2436,81 +2656,7 @@ qs_status qs_stream_run(qs_ctx *c, qs_stream *s, qs_mode mode, qs_stats *stats) 
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        uint64_t rescans = 0, resumed = 0;
-        if (eng == QS_ENGINE_LOOKAHEAD && c->last_waits) {
-            uint64_t w = 0;  // a resolver gave up waiting for its window's lists (device hand-off)
-            HIPCHK(hipMemcpy(&w, c->hand.as<uint64_t>() + 2, 8, hipMemcpyDeviceToHost));
-            if (inject_once(c, "handoff", kInjHandoff)) w = 1;  // test hook: a timed-out hand-off
-            if (w) {
-                // the select stream did not run beside the resolvers (e.g. a profiler serialising
-                // dispatches), or a mailbox peer never posted: the run's results and table updates
-                // are void and the device table is rebuilt from the host mirror (guarded(), as for
-                // a device fault); an unsharded context uses cross-stream events from now on
-                if (c->last_resident) {
-                    ++c->res_timeouts;
-                    c->res_cooldown = true;
-                } else if (!c->mbox_on) {
-                    c->handoff_off = true;
-                }
-                if (c->mbox_on && !c->comm) c->mbox_broken = true;
-                fail(QS_ETIMEOUT, c->mbox_on ? "mailbox exchange timed out (a peer never posted its window)"
-                                             : c->last_resident
-                                                   ? "resident lookahead stream timed out (a hand-off never arrived); "
-                                                     "the next run uses per-window launches"
-                                                   : "lookahead window hand-off timed out (lists never published); "
-                                                     "the context falls back to stream events");
-            }
-        }
-        // a resident run that finished without a timeout: only CONSECUTIVE resident timeouts keep
-        // the context on per-window launches (qs_ctx.hpp)
-        if (eng == QS_ENGINE_LOOKAHEAD && c->last_resident) c->res_timeouts = 0;
-        if (eng == QS_ENGINE_LOOKAHEAD && c->nfall.p) {
-            uint64_t h[2] = {0, 0};
-            HIPCHK(hipMemcpy(h, c->nfall.p, 16, hipMemcpyDeviceToHost));
-            rescans = h[0];
-            resumed = h[1];
-            if (getenv("QS_NORM_DIAG"))
-                fprintf(stderr, "QS_NORM_DIAG rescans %llu resumed windows %llu\n", (unsigned long long)h[0],
-                        (unsigned long long)h[1]);
-        }
-        c->mirror_stale = true;
-        if (eng != QS_ENGINE_SCAN) c->soa_valid = false;  // those engines update the rows only
-        kt.finish();
-        maybe_inject_fault(c, "stream_run");
-        // keep the host mirror authoritative after every stream (one D2H of the rows, outside
-        // the timed region): a later device fault rebuilds the table from it
-        sync_mirror(c);
-        if (c->aa_track && P > 0 && n > 0) {
-            // fold the run's placements into the mirror's anti-affinity state (4 P bytes back, outside
-            // wall_s): the mirror stays authoritative for save / restore and the recovery rebuild
-            std::vector<int32_t> node(P);
-            HIPCHK(hipMemcpy(node.data(), s->d_node.p, 4 * (size_t)P, hipMemcpyDeviceToHost));
-            for (uint32_t k = 0; k < P; k++)
-                if (node[k] >= 0 && (uint32_t)node[k] < n)
-                    c->m.aa_add((uint32_t)s->pods[s->order[k]].app, (uint32_t)node[k], +1);
-        }
-        s->aa_ran = aa_exact;
-        s->ran = true;
-        s->mode_ran = (int)mode;
-        s->epoch_after = ++c->table_epoch;
-        if (stats) {
-            std::memset(stats, 0, sizeof(*stats));
-            for (int k = 0; k < 4; k++) {
-                stats->kernel_s[k] = kt.secs[k];
-                stats->kernel_launches[k] = kt.count[k];
-            }
-            stats->pods = P;
-            stats->evals = (uint64_t)P * n;
-            stats->wall_s = ms * 1e-3;
-            stats->batches = batches;
-            stats->truncations = rescans;
-            stats->engine_used = eng;
-            stats->table_layout = c->wide ? 1 : 0;
-            stats->resumed_windows = resumed;
-            stats->resident = (eng == QS_ENGINE_LOOKAHEAD && c->last_resident) ? 1 : 0;
-            stats->resident_path = stats->resident ? c->last_res_path : 0;
-            stats->device_faults = c->device_faults;
-        }
+        finish_run(c, s, mode, plan, kn, kt, batches, ms, stats);
     });
 }
 
