@@ -159,6 +159,10 @@ struct qs_stream {
     // first kHostSpreadApps of them) with their number (above kHostSpreadApps the stream runs SCAN)
     int32_t host_row[16];
     uint32_t host_apps = 0;
+    // ... 1 = a spread pod of any of the three kinds that restricts (nodeSelector or required terms)
+    // under nodeAffinityPolicy Honor (spec S16), as the context's policy stood at prepare, and their number
+    std::vector<uint8_t> honors;
+    uint32_t honor_pods = 0;
     int shift = 0;
     bool wide = false;  // pod records are DPodW (the table's wide layout) when set
     // Uniform windows: run0[k] = first stream position of the run of byte-identical
@@ -210,6 +214,9 @@ struct qs_ctx {
     // array is rebuilt from the mirror before the next launch that reads it.
     qs_host::DevBuf hcount, hc_idx, hc_val;
     bool hc_valid = false;
+    // nodeAffinityPolicy of the spread constraints (qs_set_topology_spread_node_affinity_policy, spec S16):
+    // QS_POLICY_IGNORE or QS_POLICY_HONOR.  Resolved on the host into bit 11 of a pod's record.
+    int32_t spread_policy = 0;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

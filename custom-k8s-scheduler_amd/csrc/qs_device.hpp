@@ -72,6 +72,11 @@ static_assert(kSpreadApps <= kMaxZones, "the spread apps fill one row");
 // address of the uint16 (app, node) counts (null: the context keeps none), words 16-31 the hostname-spread
 // apps of a PERSISTENT stream (kHostSpreadApps entries, -1 = unused; the LDS slots of k_persistent<..., HOST>).
 constexpr uint32_t kHostSpreadApps = 16;
+// The score path's device words (qs_ctx::score_gs, zero between calls): u64 words 0-5 {best, arrivals,
+// taint max, affinity max, feasible zones, inverted hostname minimum}; word kGsDom the domain word of the
+// Honor count pass (spec S16) and from word kGsCnt its kMaxZones uint32 sums.
+constexpr uint32_t kGsDom = 6, kGsCnt = 8;
+constexpr size_t score_gs_bytes() { return (kGsCnt + kMaxZones / 2) * 8; }
 struct DevTable {
     DRow *rows;       // compact layout (nullptr in the wide layout)
     DRowW *wrows;     // wide layout (nullptr in the compact layout)

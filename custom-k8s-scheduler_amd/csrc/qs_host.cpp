@@ -467,10 +467,11 @@ void ensure_hcount(qs_ctx *c) {
     aa_check_table(c);
     if (c->hcount.p && c->hc_valid) return;
     if (c->cap > kHcMaxNodes)
-        fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME keeps 2 KB of counts per node: tables up to 2^19 nodes");
+        fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and a restricting spread pod under nodeAffinityPolicy Honor) keeps "
+                        "2 KB of counts per node: tables up to 2^19 nodes");
     for (uint32_t i = 0; i < c->m.n; i++)
         if (c->m.mp[i] > kHcMaxPods)
-            fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME counts pods per node in 16 bits: node " + std::to_string(i) +
+            fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and nodeAffinityPolicy Honor) counts pods per node in 16 bits: node " + std::to_string(i) +
                                 " has max_pods above 65535");
     const size_t cells = (size_t)kMaxApps * c->cap;
     const void *before = c->hcount.p;
@@ -666,13 +667,23 @@ bool pod_host_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_HOSTKE
 // bits 26-30: max_skew of a QS_AA_SPREAD pod (0 for every other kind; spec S13, read by the kFeatAA
 // kernels only).  Bit 31 stays the batched claim's.  A QS_AA_SPREAD_SOFT pod (spec S14) carries kind 0,
 // so that no filter knows it, bit 14, and its max_skew; a QS_AA_SPREAD_HOSTNAME pod (spec S15) likewise
-// kind 0, bit 15, and its max_skew.  Bits 7 and 11 stay free in the record (the score path's launcher
-// uses bit 7 of its own copy).
+// kind 0, bit 15, and its max_skew.  Bit 11: a spread pod of any kind that restricts under
+// nodeAffinityPolicy Honor (spec S16; pod_honors below), read by the kFeatAA kernels of the normalizing
+// classes only.  Bit 7 stays free in the record (the score path's launcher uses bits 7 and 31 of its own
+// copy).
+// A pod restricts when it has a nodeSelector or required node-affinity terms (spec S16); the policy is
+// HONOR only on a context whose NodeAffinity filter is on, so M(pod) is what that filter admits.  It is
+// read on a context that tracks only (tracking cannot change while prepared streams exist), so the
+// records of every other context are what they were.
+bool pod_honors(const qs_ctx *c, const qs_pod &p) {
+    return c->aa_track && c->spread_policy == QS_POLICY_HONOR && c->cfg.enable_affinity && pod_spreads(p) &&
+           ((p.sel[0] | p.sel[1]) != 0 || p.n_req_terms > 0);
+}
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
     const bool soft = pod_soft_spread(p), host = pod_host_spread(p);
     return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
-           (aff * (uint32_t)p.n_pref_terms << 8) |
+           (aff * (uint32_t)p.n_pref_terms << 8) | ((pod_honors(c, p) ? 1u : 0u) << 11) |
            ((soft || host ? 0u : (uint32_t)QS_AA_KIND(p.anti_affinity)) << 12) | ((soft ? 1u : 0u) << 14) |
            ((host ? 1u : 0u) << 15) | ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
 }
@@ -927,7 +938,7 @@ struct KernelTimer {
 uint32_t la_window(const qs_ctx *c);
 bool la_overlap(const qs_ctx *c);
 
-int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host_over = false) {
+int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host_over = false, bool honor = false) {
     int e = c->cfg.engine;
     const uint32_t feat = c->dc.feat;
     if (feat & kFeatAA) {
@@ -947,9 +958,14 @@ int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host
             fail(QS_EINVAL, "PERSISTENT engine supports QS_AA_SPREAD_HOSTNAME pods of at most " +
                                 std::to_string(kHostSpreadApps) + " distinct apps per stream, and not together "
                                 "with QS_AA_SPREAD_SOFT pods");
+        // nodeAffinityPolicy Honor (spec S16): the per-pod count pass over the nodes the pod's selector
+        // admits exists on SCAN and the score path only
+        if (honor && e == QS_ENGINE_PERSISTENT)
+            fail(QS_EINVAL, "PERSISTENT engine does not count topology spread under nodeAffinityPolicy Honor: a stream "
+                            "that holds a spread pod with a nodeSelector or required node-affinity terms runs SCAN");
         if (e == QS_ENGINE_AUTO)
-            e = n <= persistent_max_nodes(feat) && !spread_over && !host_over ? QS_ENGINE_PERSISTENT
-                                                                               : QS_ENGINE_SCAN;
+            e = n <= persistent_max_nodes(feat) && !spread_over && !host_over && !honor ? QS_ENGINE_PERSISTENT
+                                                                                         : QS_ENGINE_SCAN;
     }
     if (e == QS_ENGINE_AUTO) {
         if (n > 0 && la_geometry(n, la_window(c), shard_plan(c).W, 2 * la_window(c)).G > 0)
@@ -1006,8 +1022,10 @@ struct RunPlan {
     uint32_t feat;     // c->dc.feat of the run
     bool aa_exact;     // an exact stream of a tracking context: it carries the filter and records its pods
     bool spread_over;  // more SPREAD apps than k_persistent keeps zone counts for
-    bool host_spread;  // the stream holds hostname-spread pods (and the context tracks)
-    bool host_over;    // ... of more apps than k_persistent's slots, or beside soft-spread pods
+    bool host_spread;  // the stream needs the per-(app, node) counts: hostname-spread pods, or restricting
+                       // spread pods under nodeAffinityPolicy Honor (and the context tracks)
+    bool host_over;    // hostname-spread pods of more apps than k_persistent's slots, or beside soft-spread pods
+    bool honor;        // the stream holds a restricting spread pod under Honor (spec S16): it runs SCAN
 };
 
 RunPlan plan_run(qs_ctx *c, const qs_stream *s, qs_mode mode) {
@@ -1027,11 +1045,16 @@ RunPlan plan_run(qs_ctx *c, const qs_stream *s, qs_mode mode) {
     // hostname topology spread (spec S15): the k_persistent instantiations that keep the (app, node)
     // counts of the stream's hostname-spread apps in LDS (kFeatHost), for at most kHostSpreadApps apps
     // and no soft pod in the same stream
-    p.host_spread = p.aa_exact && s->host_pods != 0;
+    const bool host_pods = p.aa_exact && s->host_pods != 0;
     const bool has_soft = p.aa_exact && (c->dc.feat & kFeatSoft) != 0;
-    p.host_over = p.host_spread && (s->host_apps > kHostSpreadApps || has_soft);
-    if (p.host_spread && !p.host_over) c->dc.feat |= kFeatHost;
-    p.eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED : pick_engine(c, c->m.n, p.spread_over, p.host_over);
+    p.host_over = host_pods && (s->host_apps > kHostSpreadApps || has_soft);
+    // nodeAffinityPolicy Honor (spec S16): a stream with a restricting spread pod counts over the
+    // per-node array in a pass of its own, which SCAN has and k_persistent has not
+    p.honor = p.aa_exact && s->honor_pods != 0;
+    p.host_spread = host_pods || p.honor;
+    if (host_pods && !p.host_over && !p.honor) c->dc.feat |= kFeatHost;
+    p.eng = mode == QS_MODE_BATCHED ? QS_ENGINE_BATCHED
+                                    : pick_engine(c, c->m.n, p.spread_over, p.host_over, p.honor);
     p.feat = c->dc.feat;
     return p;
 }
@@ -1168,7 +1191,10 @@ uint64_t run_scan(qs_ctx *c, const qs_stream *s, const RunIo &io, bool aa_exact,
     for (uint32_t k = 0; k < P; k++) {
         // (128: a soft-spread pod of a tracked stream, spec S14: the pre-pass in every class)
         // (256: a hostname-spread pod, spec S15: the pre-pass for the minimum of its app's counts)
-        const int sp = !aa_exact ? 0 : s->soft[k] ? 128 : s->hosts[k] ? 256 : 0;
+        // (512: a restricting SPREAD / SPREAD_SOFT pod under nodeAffinityPolicy Honor, spec S16: the count
+        // pass first; a hostname-spread pod's minimum launch reads the record's bit instead)
+        const int sp = !aa_exact ? 0
+                                 : (s->soft[k] ? 128 : s->hosts[k] ? 256 : 0) | (s->honors[k] && !s->hosts[k] ? 512 : 0);
         kt.begin(1, c->stream);  // the key scan alone (+ normalize pre-pass)
         HIPCHK(launch_scan_pod(c->dt, io.dp, io.dx, k, c->dc, c->scratch.p, io.on, io.ok, io.st,
                                nullptr, nullptr, nullptr, 1 | sp, c->stream));
@@ -2016,6 +2042,26 @@ qs_status qs_get_topology_spread_weight(qs_ctx *c, int32_t *w) {
     });
 }
 
+qs_status qs_set_topology_spread_node_affinity_policy(qs_ctx *c, int32_t policy) {
+    return guarded(c, [&] {
+        if (!c->streams.empty())
+            fail(QS_ESTATE, "the topology spread nodeAffinityPolicy cannot change while prepared streams exist");
+        if (policy != QS_POLICY_IGNORE && policy != QS_POLICY_HONOR)
+            fail(QS_EINVAL, "the topology spread nodeAffinityPolicy must be QS_POLICY_IGNORE or QS_POLICY_HONOR");
+        if (policy == QS_POLICY_HONOR && !c->cfg.enable_affinity)
+            fail(QS_EINVAL, "QS_POLICY_HONOR needs the NodeAffinity filter (config.enable_affinity = 1): it counts "
+                            "the nodes that filter admits");
+        c->spread_policy = policy;
+    });
+}
+
+qs_status qs_get_topology_spread_node_affinity_policy(qs_ctx *c, int32_t *policy) {
+    return guarded(c, [&] {
+        if (!policy) fail(QS_EINVAL, "null output");
+        *policy = c->spread_policy;
+    });
+}
+
 qs_status qs_score_pod_zone_scores(qs_ctx *c, int32_t *out) {
     return guarded(c, [&] {
         if (!out) fail(QS_EINVAL, "null output");
@@ -2112,7 +2158,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         check_row_values(one, 0);
         if (c->hcount.p && r->max_pods > kHcMaxPods)
             fail(QS_EINVAL, "max_pods above 65535 on a context that counts pods per (app, node) in 16 bits "
-                            "(QS_AA_SPREAD_HOSTNAME, spec S15)");
+                            "(QS_AA_SPREAD_HOSTNAME, spec S15; nodeAffinityPolicy Honor, spec S16)");
         if (c->aa_track && idx < m.n && r->zone != m.zone[idx] && m.aa_holds(idx))
             fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
                             "cannot change while tracking is on");
@@ -2436,7 +2482,8 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
         return nullptr;
     }
     // a hostname-spread pod (spec S15) reads the (app, node) counts: allocated / rebuilt first
-    if (c->aa_track && pod_host_spread(*pod)) ensure_hcount(c);
+    // ... and so does a restricting spread pod of any kind under nodeAffinityPolicy Honor (spec S16)
+    if (c->aa_track && (pod_host_spread(*pod) || pod_honors(c, *pod))) ensure_hcount(c);
     const DPodX dx = compact_podx(c, *pod);
     // (behind the packed words: the 64 zone scores of a soft-spread pod, spec S14)
     const size_t pb = score_pod1_pack_bytes(n) + kMaxZones * 4;
@@ -2450,8 +2497,10 @@ static const uint32_t *score_pod_launch(qs_ctx *c, const qs_pod *pod, uint32_t w
         std::memset(c->pin, 0, pb);
     }
     if (!c->score_gs.p) {
-        c->score_gs.ensure(64);  // (+ the feasible-zones word of a soft-spread pod, the minimum of a hostname-spread pod)
-        HIPCHK(hipMemsetAsync(c->score_gs.p, 0, 64, c->stream));
+        // (+ the feasible-zones word of a soft-spread pod, the minimum of a hostname-spread pod, and the
+        // domain word and 64 counts of the Honor count pass, spec S16)
+        c->score_gs.ensure(score_gs_bytes());
+        HIPCHK(hipMemsetAsync(c->score_gs.p, 0, score_gs_bytes(), c->stream));
     }
     const uint32_t pidx = c->pend < n ? c->pend : 0xFFFFFFFFu;
     const HostRow prow = pidx < n ? compact_row(c->m, pidx, c->shift, c->wide) : HostRow{};
@@ -2550,6 +2599,8 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
         std::vector<DPodX> dx(needx ? std::max<uint32_t>(p, 1) : 1);
         s->soft.assign(p, 0);
         s->hosts.assign(p, 0);
+        s->honors.assign(p, 0);
+        s->honor_pods = 0;
         s->host_pods = 0;
         s->host_apps = 0;
         std::fill(std::begin(s->host_row), std::end(s->host_row), -1);
@@ -2559,6 +2610,8 @@ qs_status qs_stream_prepare(qs_ctx *c, const qs_pod *pods, uint32_t p, qs_stream
             s->soft[k] = pod_soft_spread(pods[j]) ? 1 : 0;
             s->hosts[k] = pod_host_spread(pods[j]) ? 1 : 0;
             s->host_pods += s->hosts[k];
+            s->honors[k] = pod_honors(c, pods[j]) ? 1 : 0;
+            s->honor_pods += s->honors[k];
             if (s->hosts[k] && !host_seen[(uint32_t)pods[j].app]) {  // the distinct apps, for k_persistent's slots
                 host_seen[(uint32_t)pods[j].app] = 1;
                 if (s->host_apps < kHostSpreadApps) s->host_row[s->host_apps] = pods[j].app;

@@ -160,12 +160,15 @@ __device__ __forceinline__ uint8_t *aa_lds_zscore() {
 // The wave's zone scores of a soft pod from the global counts (SCAN and the score path; the counts of
 // the pod's turn and fz are a kernel boundary behind) into the wave's LDS bytes; nullptr for every
 // other pod.  Call it with every lane active.  The returned bytes are read by this wave only.
+// hcnt (spec S16): the count pass's sums cH[z] of a restricting pod under nodeAffinityPolicy Honor, which
+// then stand in for the app's zone counts; nullptr for every other pod.
 template <int NW>
-__device__ __forceinline__ const uint8_t *soft_zone_bytes(const DevTable &t, uint32_t flags, uint64_t fz) {
+__device__ __forceinline__ const uint8_t *soft_zone_bytes(const DevTable &t, uint32_t flags, uint64_t fz,
+                                                          const uint32_t *hcnt = nullptr) {
     if (!pod_soft(flags)) return nullptr;
     uint8_t *zs = aa_lds_zscore<NW>();
     const uint32_t z = threadIdx.x & 63u;
-    const int32_t cz = t.zcount[pod_app(flags) * kMaxZones + z];
+    const int32_t cz = hcnt ? (int32_t)hcnt[z] : t.zcount[pod_app(flags) * kMaxZones + z];
     zs[z] = (uint8_t)(fz ? soft_zone_score(cz, fz, pod_skew(flags), aa_logtab(t)) : kNoZoneScore);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -203,6 +206,86 @@ __device__ __forceinline__ const uint16_t *hs_row(const DevTable &t, uint32_t fl
 // cnt + 1 - m <= skew with inv = kHsInv - m, in unsigned arithmetic without a subtraction
 __device__ __forceinline__ bool hs_ok(uint32_t cnt, uint32_t inv, uint32_t flags) {
     return cnt + 1u + inv <= pod_skew(flags) + kHsInv;
+}
+
+// nodeAffinityPolicy Honor (spec S16).  Pod-record bit 11, resolved on the host: the context's policy is
+// HONOR and the pod is a spread pod of any of the three kinds with a nodeSelector or required terms.  For
+// such a pod only the nodes of M(pod), those that pass the NodeAffinity filter's predicate, are counted
+// and make up the domains.  SCAN and the score path take the 64 sums cH[z] and the domain word in a
+// launch of the pre-pass of its own (the count pass; marks below) from the uint16 (app, node) counts of
+// spec S15, and spread_word_h / soft_zone_bytes then read them in place of zcount and the domain row.  A
+// hostname-spread pod needs no such launch: its minimum launch skips the nodes outside M.  Only classes
+// with kFeatAffinity carry any of this (the policy needs the filter): every other class compiles to the
+// code it compiled to before.
+constexpr uint32_t kHonorBit = 1u << 11;
+// the count pass's marks: bit 30 of k_scan_norm's pod index (bit 31 is the hostname minimum's), and bit
+// 31 of the score path's by-value copy of the pod (the batched claim's bit in its own staged copies, free
+// here; bit 7 is the hostname minimum's)
+constexpr uint32_t kHonorScanPass = 0x40000000u, kHonorCntPass = 1u << 31;
+template <uint32_t F>
+constexpr bool kHonorF = (F & kFeatAA) != 0 && (F & kFeatAffinity) != 0;
+__host__ __device__ __forceinline__ bool pod_honor(uint32_t flags) { return (flags & kHonorBit) != 0; }
+// i in M(pod): the kFeatAffinity part of feasible<F> on its own
+template <class P>
+__device__ __forceinline__ bool honor_match(const RowX &x, const P &p, const DPodX &px) {
+    bool ok = true;
+    const uint64_t s0 = uniform64(px.sel0), s1 = uniform64(px.sel1);
+    if (s0 | s1) ok &= subset128(s0, s1, x.lb0, x.lb1);
+    const uint32_t nt = (uint32_t)__builtin_amdgcn_readfirstlane((int)((p.flags >> 4) & 7u));
+    if (nt != 0) {
+        bool any = false;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k)
+            if (k < nt) any |= subset128(px.req[k][0], px.req[k][1], x.lb0, x.lb1);
+        ok &= any;
+    }
+    return ok;
+}
+// The count pass of one workgroup of NW waves; every thread calls it (two barriers).  `nodes(visit)` runs
+// the caller's node loop and calls visit(i, zone) for each node of M this thread owns.  Per workgroup 64
+// LDS bins take the non-zero count cells with LDS atomic adds (most cells are 0 and are skipped), the
+// zones of M meet in a DPP wave OR and one LDS word per wave; behind the barrier at most 64 global
+// atomic adds and one atomic OR leave the workgroup, never one per node (see ScanScratch).  Integer sums:
+// the order does not matter, the result is exact.  row: the app's count row (nullptr: nothing recorded).
+template <int NW, class Nodes>
+__device__ __forceinline__ void honor_count(const uint16_t *row, uint32_t *gcnt, uint64_t *gdom, Nodes &&nodes) {
+    __shared__ uint32_t bins[kMaxZones];
+    __shared__ uint64_t wdom[NW];
+    const uint32_t tid = threadIdx.x;
+    if (tid < kMaxZones) bins[tid] = 0;
+    __syncthreads();
+    uint64_t dom = 0;
+    nodes([&](uint32_t i, uint32_t zone) {
+        zone &= kMaxZones - 1u;
+        dom |= 1ull << zone;
+        const uint32_t cnt = row ? row[i] : 0u;
+        if (cnt) atomicAdd(&bins[zone], cnt);
+    });
+    dom = wave_or_u64(dom);  // (the node loop is over: every lane is active again)
+    if ((tid & 63u) == 0) wdom[tid >> 6] = dom;
+    __syncthreads();
+    if (tid < kMaxZones && bins[tid] != 0)
+        __hip_atomic_fetch_add(gcnt + tid, bins[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) {
+        uint64_t d = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) d |= wdom[w];
+        if (d) __hip_atomic_fetch_or(gdom, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// spread_word for the kernels behind a count pass: a restricting SPREAD pod under Honor takes the counts
+// and the domain flags from the pass's results (a kernel boundary behind), every other pod from zcount
+// and the domain row as before.  Every lane of the wave must be active.
+template <uint32_t F>
+__device__ __forceinline__ uint64_t spread_word_h(const DevTable &t, uint32_t flags, const uint32_t *hcnt,
+                                                  const uint64_t *hdom) {
+    if constexpr (kHonorF<F>) {
+        if (pod_aa(flags) == 3u && pod_honor(flags)) {
+            const uint32_t z = threadIdx.x & 63u;
+            return spread_allowed((int32_t)hcnt[z], ((*hdom >> z) & 1ull) != 0, pod_skew(flags));
+        }
+    }
+    return spread_word(t, flags);
 }
 
 // SOFT (kFeatAA classes only): the instantiation of a stream that holds soft-spread pods (spec S14,
@@ -582,6 +665,10 @@ struct ScanScratch {
     // hostname-spread pods (spec S15): the inverted minimum of the app's node counts (k_scan_norm; 0 =
     // none), reset with fz
     uint32_t hmin;
+    // nodeAffinityPolicy Honor (spec S16): the count pass's sums cH[z] over the nodes of M(pod) and the
+    // zones of M (k_scan_norm's marked launch), reset with fz / hmin for a pod that carries the bit
+    uint32_t hcnt[kMaxZones];
+    uint64_t hdom;
 };
 static_assert(offsetof(ScanScratch, lo) == offsetof(ScanHead, lo) && offsetof(ScanScratch, mt) == offsetof(ScanHead, mt),
               "ScanHead mirrors ScanScratch");
@@ -604,8 +691,10 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
                                                    const DPodX *__restrict__ podx, uint32_t s,
                                                    ScanScratch *sc) {
     // (kFeatAA classes: bit 31 of s marks the launch that takes a hostname-spread pod's minimum, below)
-    [[maybe_unused]] bool minpass = false;
-    if constexpr ((F & kFeatAA) != 0) { minpass = (s >> 31) != 0; s &= 0x7FFFFFFFu; }
+    // (classes with kFeatAffinity too: bit 30 marks the count pass of nodeAffinityPolicy Honor, spec S16)
+    [[maybe_unused]] bool minpass = false, cntpass = false;
+    if constexpr (kHonorF<F>) { minpass = (s >> 31) != 0; cntpass = (s & kHonorScanPass) != 0; s &= 0x3FFFFFFFu; }
+    else if constexpr ((F & kFeatAA) != 0) { minpass = (s >> 31) != 0; s &= 0x7FFFFFFFu; }
     const PodT<F> p = pods[s];
     // (a kFeatAA class without the normalizing plugins runs this pre-pass for soft-spread pods only,
     // spec S14, and has no extension records)
@@ -613,6 +702,17 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
         if constexpr ((F & kFeatAA) != 0 && (F & kFeatNorm) == 0) return DPodX{};
         else return podx[s];
     }();
+    if constexpr (kHonorF<F>) {
+        if (cntpass) {  // (workgroup-uniform) the sums and the domains over M(pod), nothing else
+            const uint16_t *h = aa_hcount(t);
+            const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
+            honor_count<4>(h ? h + (size_t)pod_app(p.flags) * t.cap : nullptr, sc->hcnt, &sc->hdom, [&](auto &&visit) {
+                for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256)
+                    if (honor_match(load_rowx<F>(t, i), p, px)) visit(i, (uint32_t)t.zone[i]);
+            });
+            return;
+        }
+    }
     uint32_t lt = 0, la = 0;
     [[maybe_unused]] uint64_t zw = ~0ull;  // SPREAD pods: the allowed zones (spec S13), once per wave
     [[maybe_unused]] uint64_t lz = 0;      // soft-spread pods: the zones of this lane's feasible nodes (spec S14)
@@ -624,11 +724,13 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
     // the nodes that pass the skew test too.
     [[maybe_unused]] const uint16_t *hc = nullptr;
     [[maybe_unused]] uint32_t lh = 0, hm = 0;
+    [[maybe_unused]] bool honor = false;  // (wave-uniform) a restricting pod under Honor (spec S16)
     if constexpr ((F & kFeatAA) != 0) {
-        zw = spread_word(t, p.flags);
+        zw = spread_word_h<F>(t, p.flags, sc->hcnt, &sc->hdom);
         soft = pod_soft(p.flags);
         hc = hs_row(t, p.flags);
         if (hc && !minpass) hm = sc->hmin;
+        if constexpr (kHonorF<F>) honor = pod_honor(p.flags);
     }
     const uint32_t lo = sc->lo, hi = sc->hi ? sc->hi : t.n;
     for (uint32_t i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) {
@@ -640,7 +742,9 @@ __global__ __launch_bounds__(256) void k_scan_norm(DevTable t, const PodT<F> *__
             if (hc) {
                 const uint32_t cnt = hc[i];
                 if (minpass) {  // the minimum's launch: every node counts, nothing else is reduced
-                    const uint32_t u = kHsInv - cnt;
+                    uint32_t u = kHsInv - cnt;
+                    // (under Honor, spec S16: every node of M(pod), and no other)
+                    if constexpr (kHonorF<F>) { if (honor && !honor_match(x, p, px)) u = 0; }
                     lh = u > lh ? u : lh;
                     f = false;
                 } else {
@@ -691,8 +795,11 @@ __global__ __launch_bounds__(256) void k_scan_key(DevTable t, const PodT<F> *__r
     [[maybe_unused]] const uint8_t *zs = nullptr;
     [[maybe_unused]] uint32_t wpts = 0;
     if constexpr ((F & kFeatAA) != 0) {
-        zw = spread_word(t, p.flags);
-        zs = soft_zone_bytes<4>(t, p.flags, pod_soft(p.flags) ? sc->fz : 0ull);
+        zw = spread_word_h<F>(t, p.flags, sc->hcnt, &sc->hdom);
+        // (a restricting soft pod under Honor, spec S16: the count pass's sums for the zone counts)
+        const uint32_t *hcnt = nullptr;
+        if constexpr (kHonorF<F>) { if (pod_honor(p.flags)) hcnt = sc->hcnt; }
+        zs = soft_zone_bytes<4>(t, p.flags, pod_soft(p.flags) ? sc->fz : 0ull, hcnt);
         if (zs) wpts = aa_wpts(t);
     }
     // hostname-spread pods (spec S15): the app's count row and k_scan_norm's inverted minimum
@@ -832,6 +939,14 @@ __global__ __launch_bounds__(256) void k_scan_commit(DevTable t, const PodT<F> *
     sc->mt = 0;
     sc->ma = 0;
     if constexpr ((F & kFeatAA) != 0) { sc->fz = 0; sc->hmin = 0; }
+    if constexpr (kHonorF<F>) {
+        // the count pass's results (spec S16) of a pod that carries the bit: the next such pod adds to zeros
+        if (pod_honor(pods[s].flags)) {
+#pragma unroll 4
+            for (uint32_t z = 0; z < kMaxZones; ++z) sc->hcnt[z] = 0;
+            sc->hdom = 0;
+        }
+    }
     if (!out_node) return;
     const PodT<F> p = pods[s];
     if (ks) {
@@ -1011,9 +1126,28 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     // and in a normalizing class one more for the maxima under the skew test
     [[maybe_unused]] const uint16_t *hc = nullptr;
     [[maybe_unused]] uint32_t lh = 0, hm = 0;
-    [[maybe_unused]] bool minpass = false;
+    [[maybe_unused]] bool minpass = false, honor = false;
+    if constexpr (kHonorF<F>) {
+        // the count pass of nodeAffinityPolicy Honor (spec S16; kHonorCntPass in the launcher's copy of the
+        // pod, workgroup-uniform): the sums and the domains over M(pod) into the words behind gs[5]
+        if ((p.flags & kHonorCntPass) != 0) {
+            const uint16_t *h = aa_hcount(t);
+            honor_count<kScorePodGT / kWave>(h ? h + (size_t)pod_app(p.flags) * t.cap : nullptr,
+                                             reinterpret_cast<uint32_t *>(gs + kGsCnt), gs + kGsDom, [&](auto &&visit) {
+                if (i < n) {
+                    RowT<F> r;
+                    RowX x;
+                    if (i == pidx) host_row_regs<F>(prow, r, x);
+                    else x = load_rowx<F>(t, i);
+                    if (honor_match(x, p, px)) visit(i, (uint32_t)(i == pidx ? prow.zone : t.zone[i]));
+                }
+            });
+            return;
+        }
+        honor = pod_honor(p.flags);
+    }
     if constexpr ((F & kFeatAA) != 0) {
-        zw = spread_word(t, p.flags);
+        zw = spread_word_h<F>(t, p.flags, reinterpret_cast<const uint32_t *>(gs + kGsCnt), gs + kGsDom);
         hc = hs_row(t, p.flags);
         minpass = (p.flags & kHsMinPass) != 0;
         if (hc && !minpass) hm = (uint32_t)__hip_atomic_load(gs + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1034,6 +1168,8 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
                 const uint32_t cnt = hc[i];
                 if (minpass) {
                     lh = kHsInv - cnt;
+                    // (under Honor, spec S16: every node of M(pod), and no other)
+                    if constexpr (kHonorF<F>) { if (honor && !honor_match(x, p, px)) lh = 0; }
                     f = false;
                 } else {
                     f = f && hs_ok(cnt, hm, p.flags);
@@ -1078,10 +1214,13 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
     [[maybe_unused]] const uint8_t *zs = nullptr;
     [[maybe_unused]] uint32_t wpts = 0;
     if constexpr ((F & kFeatAA) != 0) {
-        zw = spread_word(t, p.flags);
+        zw = spread_word_h<F>(t, p.flags, reinterpret_cast<const uint32_t *>(gs + kGsCnt), gs + kGsDom);
         uint64_t fz = 0;
         if (pod_soft(p.flags)) fz = __hip_atomic_load(gs + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        zs = soft_zone_bytes<NW>(t, p.flags, fz);
+        // (a restricting soft pod under Honor, spec S16: the count pass's sums for the zone counts)
+        const uint32_t *hcnt = nullptr;
+        if constexpr (kHonorF<F>) { if (pod_honor(p.flags)) hcnt = reinterpret_cast<const uint32_t *>(gs + kGsCnt); }
+        zs = soft_zone_bytes<NW>(t, p.flags, fz, hcnt);
         if (zs) {
             wpts = aa_wpts(t);
             if (blockIdx.x == 0 && wv == 0)
@@ -1147,6 +1286,13 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg(DevTable t, PodT<F> 
             if constexpr ((F & kFeatAA) != 0) {
                 __hip_atomic_store(gs + 4, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(gs + 5, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if constexpr (kHonorF<F>) {  // the count pass's words (spec S16): every workgroup read them before arriving
+                if (pod_honor(p.flags)) {
+                    __hip_atomic_store(gs + kGsDom, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    for (uint32_t k = 0; k < kMaxZones / 2; ++k)
+                        __hip_atomic_store(gs + kGsCnt + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
             *reinterpret_cast<volatile uint64_t *>(hout) = b;
             __threadfence_system();
@@ -5059,6 +5205,11 @@ static hipError_t scan_pod_f(const DevTable &t, const void *pods_, const DPodX *
             }
         }
         if (!soa || softp) {
+            // part & 512 (classes with kFeatAffinity): pod s is a restricting SPREAD / SPREAD_SOFT pod under
+            // nodeAffinityPolicy Honor (spec S16): the count pass first, one more launch of the pre-pass
+            if (kHonorF<F> && (part & 512) != 0)
+                hipLaunchKernelGGL((k_scan_norm<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx,
+                                   s | kHonorScanPass, sc);
             if (hsp)
                 hipLaunchKernelGGL((k_scan_norm<F>), dim3(blocks), dim3(256), 0, stream, t, pods, podx,
                                    s | 0x80000000u, sc);
@@ -5107,6 +5258,16 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
                                    prow);
             }
         }
+        if constexpr (kHonorF<F>) {
+            // a restricting SPREAD / SPREAD_SOFT pod under nodeAffinityPolicy Honor (spec S16): first the
+            // count pass (a hostname-spread pod's minimum launch above reads the record's bit instead)
+            if (pod_honor(p.flags) && !pod_hostspread(p.flags)) {
+                PodT<F> pm = p;
+                pm.flags |= kHonorCntPass;
+                hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, pm, px, gs, pidx,
+                                   prow);
+            }
+        }
         if constexpr ((F & kFeatNorm) != 0) {
             hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, p, px, gs, pidx,
                                prow);
@@ -5123,7 +5284,8 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
     if constexpr ((F & kFeatAA) != 0) {
         // the single-workgroup form carries no zone scores (the host always passes the device words)
         // ... and no minimum of a hostname-spread pod's node counts (spec S15)
-        if (pod_soft(p.flags) || pod_hostspread(p.flags)) return hipErrorInvalidValue;
+        // ... and no count pass of nodeAffinityPolicy Honor (spec S16)
+        if (pod_soft(p.flags) || pod_hostspread(p.flags) || pod_honor(p.flags)) return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL((k_score_pod1<F>), dim3(1), dim3(1024), 0, stream, t, p, px, c, hout, seq, pidx, prow);
     return hipGetLastError();

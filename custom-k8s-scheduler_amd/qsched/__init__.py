@@ -27,12 +27,13 @@ __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_stru
            "synth_generate", "shape_table", "dist_unique_id", "empty_nodes", "pod_from_containers", "compute_qos", "load",
            "QschedError", "QschedLibraryMissing", "ENGINES", "EXPORTED", "LIB_PATH",
            "aa_spread", "aa_spread_soft", "aa_spread_hostname", "aa_is_soft", "aa_is_hostkey", "QS_AA_HOSTKEY", "aa_kind", "aa_max_skew", "QS_AA_SOFT", "QS_MAX_ZONES", "QS_AA_NONE", "QS_AA_HOSTNAME", "QS_AA_ZONE", "QS_AA_SPREAD_ZONE",
-           "QS_MAX_SPREAD_SKEW"]
+           "QS_MAX_SPREAD_SKEW", "QS_POLICY_IGNORE", "QS_POLICY_HONOR", "POLICIES"]
 
-from ._abi import (QS_AA_HOSTKEY, QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
+from ._abi import (QS_POLICY_HONOR, QS_POLICY_IGNORE, QS_AA_HOSTKEY, QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
                    QS_MAX_SPREAD_SKEW, QS_MAX_ZONES)
 
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
+POLICIES = {"ignore": QS_POLICY_IGNORE, "honor": QS_POLICY_HONOR}
 
 
 def aa_spread(max_skew: int) -> int:
@@ -254,6 +255,18 @@ class Scheduler:
         w = ctypes.c_int32(-1)
         self._chk(self.lib.qs_get_topology_spread_weight(self.ctx, ctypes.byref(w)))
         return int(w.value)
+
+    def set_topology_spread_node_affinity_policy(self, policy):
+        """qs_set_topology_spread_node_affinity_policy: "ignore" / "honor" (or QS_POLICY_*), spec S16.  Under
+        "honor" a spread pod with a nodeSelector or required node-affinity terms counts, and takes its
+        domains from, the nodes that pass them only; "ignore" in a new context."""
+        pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+        self._chk(self.lib.qs_set_topology_spread_node_affinity_policy(self.ctx, pol))
+
+    def get_topology_spread_node_affinity_policy(self) -> int:
+        v = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_topology_spread_node_affinity_policy(self.ctx, ctypes.byref(v)))
+        return int(v.value)
 
     def score_pod_zone_scores(self):
         """qs_score_pod_zone_scores: int32[QS_MAX_ZONES], the PodTopologySpread score per zone of the last

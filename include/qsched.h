@@ -74,8 +74,9 @@ typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
  * honours it (spec S11); exact streams, qs_score_pod and qs_reserve / qs_unreserve honour it on a
  * context that tracks it (qs_set_pod_anti_affinity, spec S12) and ignore it otherwise.
  * QS_AA_SPREAD_ZONE (spec S13) is the zone topologySpreadConstraint with whenUnsatisfiable:
- * DoNotSchedule over the pod's own app (UP plugins/podtopologyspread Filter; nodeAffinityPolicy and
- * nodeTaintsPolicy Ignore, minDomains unset): a node is infeasible when taking it would leave its zone
+ * DoNotSchedule over the pod's own app (UP plugins/podtopologyspread Filter; nodeAffinityPolicy Ignore
+ * unless qs_set_topology_spread_node_affinity_policy says HONOR (spec S16), nodeTaintsPolicy Ignore,
+ * minDomains unset): a node is infeasible when taking it would leave its zone
  * more than max_skew pods of the app above the emptiest zone that holds a node of the table.  The kind
  * sits in the low byte of qs_pod.anti_affinity and max_skew (1..31) in bits 8-12: QS_AA_SPREAD(max_skew).
  * Upper bits must be zero for the other kinds; a pod has one kind.  Honoured like the other kinds on a
@@ -348,6 +349,25 @@ QS_API qs_status qs_get_pod_anti_affinity(qs_ctx *ctx, int32_t *on);
  * 0..100 and for null pointers. */
 QS_API qs_status qs_set_topology_spread_weight(qs_ctx *ctx, int32_t w);
 QS_API qs_status qs_get_topology_spread_weight(qs_ctx *ctx, int32_t *w);
+/* nodeAffinityPolicy of the context's topology spread constraints (spec S16; UP
+ * apis/core#TopologySpreadConstraint.NodeAffinityPolicy, podtopologyspread/common.go#matchNodeInclusionPolicies,
+ * filtering.go#calPreFilterState, scoring.go#PreScore).  QS_POLICY_IGNORE (a new context; spec S13-S15 to
+ * the letter): every node of the table counts.  QS_POLICY_HONOR (upstream's default): for a pod with a
+ * nodeSelector or required node-affinity terms, only the nodes that pass them (the NodeAffinity filter's
+ * predicate) are counted and make up the domains of QS_AA_SPREAD, QS_AA_SPREAD_SOFT and
+ * QS_AA_SPREAD_HOSTNAME pods; a pod without either is treated as under IGNORE.  Upstream carries the field
+ * per constraint; it is per context here, because qs_pod.anti_affinity has no free bit left that is not
+ * already defined as invalid, and a cluster's manifests overwhelmingly share one value.  The policy is
+ * read on a context that tracks pod anti-affinity only.  A stream that holds such a restricting spread
+ * pod under HONOR runs QS_ENGINE_SCAN (AUTO picks it; an explicit QS_ENGINE_PERSISTENT returns
+ * QS_EINVAL), and the context keeps the per-(app, node) counts of QS_AA_SPREAD_HOSTNAME with their limits
+ * (tables up to 2^19 nodes, max_pods <= 65,535).  QS_ESTATE while the context holds prepared streams;
+ * QS_EINVAL for an unknown policy, a null pointer, a null context, and for HONOR on a context opened with
+ * enable_affinity = 0 (Honor presupposes that the NodeAffinity filter removes the nodes the selector does
+ * not admit). */
+typedef enum qs_node_inclusion_policy { QS_POLICY_IGNORE = 0, QS_POLICY_HONOR = 1 } qs_node_inclusion_policy;
+QS_API qs_status qs_set_topology_spread_node_affinity_policy(qs_ctx *ctx, int32_t policy);
+QS_API qs_status qs_get_topology_spread_node_affinity_policy(qs_ctx *ctx, int32_t *policy);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);

@@ -15,6 +15,12 @@ Arms per table:
   hostspread_persistent  the aa_* arms with the HOSTNAME apps' pods turned into HOSTSPREAD(1) (hostname topology
   hostspread_scan   spread, spec S15), checked against tests/hostspread_ref.py; read beside aa_*
                     of the same run: the same pods under the one-per-node rule
+  honor_spread_scan      the spread_scan / soft_scan / hostspread_scan streams with the NodeAffinity filter on
+  honor_soft_scan        (enable_affinity = 1: the normalizing class), the nodes of zones 0 and 1 labelled and every
+  honor_hostspread_scan  pod of the converted kind selecting that label (half of the four zones), under
+                    nodeAffinityPolicy Honor (spec S16, DESIGN.md §3.8), checked against tests/honor_spread_ref.py;
+  ignore_*_scan     the same three streams under the policy Ignore: honor_* against ignore_* is the cost of
+                    the count pass (one more launch per restricting SPREAD / SPREAD_SOFT pod; none for hostname)
   plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
   plain_scan        the cost of the filter and the recording is aa_* against plain_*
 
@@ -33,7 +39,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "soft_persistent", "soft_scan",
-        "hostspread_persistent", "hostspread_scan", "plain_persistent", "plain_scan"]
+        "hostspread_persistent", "hostspread_scan", "honor_spread_scan", "honor_soft_scan", "honor_hostspread_scan",
+        "ignore_spread_scan", "ignore_soft_scan", "ignore_hostspread_scan", "plain_persistent", "plain_scan"]
 
 
 def paths(tree):
@@ -51,6 +58,12 @@ def run_arm(n, p, arm, steps, prefix):
 
     nodes, pods = synth_generate(5, n, p)
     nodes, pods = A.fold(nodes, pods, 40, 4)
+    policy = None  # honor_* / ignore_*: the arm behind the prefix with a selector on its spread pods
+    if arm.startswith(("honor_", "ignore_")):
+        policy, arm = arm.split("_", 1)
+        out_arm = policy + "_" + arm
+    else:
+        out_arm = arm
     soft = arm.startswith("soft_")
     spread = arm.startswith("spread_") or soft
     host = arm.startswith("hostspread_")
@@ -74,10 +87,23 @@ def run_arm(n, p, arm, steps, prefix):
     engine = "auto" if batched else arm.split("_")[1]
     cfg = dict(engine=engine, batch_pods=1) if batched else dict(engine=engine)
     mode = "batched" if batched else "exact"
-    out = dict(nodes=n, pods=p, arm=arm)
+    out = dict(nodes=n, pods=p, arm=out_arm)
+    if policy:
+        import honor_spread_ref as HR
+
+        nodes = {k: v.copy() for k, v in nodes.items()}
+        nodes["label_bits"][nodes["zone"] < 2, 0] |= np.uint64(1 << 8)
+        pods = pods.copy()
+        pods["sel"][(pods["anti_affinity"] & 0xFF) == 3, 0] = np.uint64(1 << 8)
+        cfg["enable_affinity"] = 1
     with Scheduler(cfg) as s:
         if tracked:
             s.set_pod_anti_affinity(True)
+        if policy:
+            if not hasattr(s, "set_topology_spread_node_affinity_policy"):  # (--tree: a tree from before S16)
+                out.update(skipped="no qs_set_topology_spread_node_affinity_policy in this tree")
+                return out
+            s.set_topology_spread_node_affinity_policy(policy)
         s.load_nodes(nodes)
         s.save_table()
         try:
@@ -93,7 +119,10 @@ def run_arm(n, p, arm, steps, prefix):
             return out
         pl, keys = head.results()
         head.free()
-        if host:
+        if policy:
+            ref = HR.run(nodes, pods[:prefix], dict(enable_affinity=1),
+                         policy=HR.HONOR if policy == "honor" else HR.IGNORE)
+        elif host:
             ref = H.run(nodes, pods[:prefix])
         elif soft:
             ref = R.run(nodes, pods[:prefix])
@@ -155,10 +184,10 @@ def main():
             if r["nodes"] != n:
                 continue
             if "skipped" in r:
-                print(f"n {n:5d} {r['arm']:17s} skipped: {r['skipped'][:90]}")
+                print(f"n {n:5d} {r['arm']:22s} skipped: {r['skipped'][:90]}")
                 continue
             rel = f"x{r['us_per_pod'] / base['us_per_pod']:.3f} of batched1" if base else ""
-            print(f"n {n:5d} {r['arm']:17s} {r['ms_per_step']:10.3f} ms  {r['us_per_pod']:8.3f} us/pod  {rel}  "
+            print(f"n {n:5d} {r['arm']:22s} {r['ms_per_step']:10.3f} ms  {r['us_per_pod']:8.3f} us/pod  {rel}  "
                   f"engine {r['engine_used']}  prefix {'ok' if r['prefix_ok'] else 'DIFFERS'}")
     return 1 if bad else 0
 
