@@ -160,7 +160,8 @@ struct qs_stream {
     int32_t host_row[16];
     uint32_t host_apps = 0;
     // ... 1 = a spread pod of any of the three kinds that restricts (nodeSelector or required terms)
-    // under nodeAffinityPolicy Honor (spec S16), as the context's policy stood at prepare, and their number
+    // under nodeAffinityPolicy Honor (spec S16) or leaves a hard taint bit untolerated under nodeTaintsPolicy
+    // Honor (spec S17), as the context's policies stood at prepare, and their number
     std::vector<uint8_t> honors;
     uint32_t honor_pods = 0;
     int shift = 0;
@@ -217,6 +218,8 @@ struct qs_ctx {
     // nodeAffinityPolicy of the spread constraints (qs_set_topology_spread_node_affinity_policy, spec S16):
     // QS_POLICY_IGNORE or QS_POLICY_HONOR.  Resolved on the host into bit 11 of a pod's record.
     int32_t spread_policy = 0;
+    // nodeTaintsPolicy likewise (qs_set_topology_spread_node_taints_policy, spec S17): resolved into bit 7
+    int32_t taints_policy = 0;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

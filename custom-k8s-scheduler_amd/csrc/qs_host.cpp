@@ -467,11 +467,11 @@ void ensure_hcount(qs_ctx *c) {
     aa_check_table(c);
     if (c->hcount.p && c->hc_valid) return;
     if (c->cap > kHcMaxNodes)
-        fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and a restricting spread pod under nodeAffinityPolicy Honor) keeps "
+        fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and a restricting spread pod under nodeAffinityPolicy / nodeTaintsPolicy Honor) keeps "
                         "2 KB of counts per node: tables up to 2^19 nodes");
     for (uint32_t i = 0; i < c->m.n; i++)
         if (c->m.mp[i] > kHcMaxPods)
-            fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and nodeAffinityPolicy Honor) counts pods per node in 16 bits: node " + std::to_string(i) +
+            fail(QS_EINVAL, "QS_AA_SPREAD_HOSTNAME (and nodeAffinityPolicy / nodeTaintsPolicy Honor) counts pods per node in 16 bits: node " + std::to_string(i) +
                                 " has max_pods above 65535");
     const size_t cells = (size_t)kMaxApps * c->cap;
     const void *before = c->hcount.p;
@@ -669,21 +669,33 @@ bool pod_host_spread(const qs_pod &p) { return pod_spreads(p) && QS_AA_IS_HOSTKE
 // so that no filter knows it, bit 14, and its max_skew; a QS_AA_SPREAD_HOSTNAME pod (spec S15) likewise
 // kind 0, bit 15, and its max_skew.  Bit 11: a spread pod of any kind that restricts under
 // nodeAffinityPolicy Honor (spec S16; pod_honors below), read by the kFeatAA kernels of the normalizing
-// classes only.  Bit 7 stays free in the record (the score path's launcher uses bits 7 and 31 of its own
-// copy).
+// classes only.  Bit 7: a spread pod of any kind that restricts by taints under nodeTaintsPolicy Honor
+// (spec S17; pod_honors_taints below), read by the same kernels.  (The score path's launcher marks its
+// passes in bits 7 and 31 of its own copy; in the classes that read bit 7 of the record, in bit 31 alone.)
 // A pod restricts when it has a nodeSelector or required node-affinity terms (spec S16); the policy is
 // HONOR only on a context whose NodeAffinity filter is on, so M(pod) is what that filter admits.  It is
 // read on a context that tracks only (tracking cannot change while prepared streams exist), so the
 // records of every other context are what they were.
-bool pod_honors(const qs_ctx *c, const qs_pod &p) {
+bool pod_honors_affinity(const qs_ctx *c, const qs_pod &p) {
     return c->aa_track && c->spread_policy == QS_POLICY_HONOR && c->cfg.enable_affinity && pod_spreads(p) &&
            ((p.sel[0] | p.sel[1]) != 0 || p.n_req_terms > 0);
 }
+// A pod restricts by taints when some hard taint bit is not tolerated: ~tol_hard != 0 (spec S17).  That
+// is a property of the pod alone: M_T may still be every node of the table as it stands (no node carries
+// such a bit), and the kernels then count what S13-S16 count, but no qs_node_upsert between prepare and
+// run can leave a record that says otherwise.  HONOR only on a context whose TaintToleration filter is on.
+bool pod_honors_taints(const qs_ctx *c, const qs_pod &p) {
+    return c->aa_track && c->taints_policy == QS_POLICY_HONOR && c->cfg.enable_taint && pod_spreads(p) &&
+           ~p.tol_hard != 0;
+}
+// ... by either predicate: what every host-side rule of S16 hangs on
+bool pod_honors(const qs_ctx *c, const qs_pod &p) { return pod_honors_affinity(c, p) || pod_honors_taints(c, p); }
 uint32_t pod_flags(const qs_ctx *c, const qs_pod &p) {
     const uint32_t aff = c->cfg.enable_affinity ? 1u : 0u;
     const bool soft = pod_soft_spread(p), host = pod_host_spread(p);
     return (uint32_t)p.qos | ((uint32_t)c->strat[p.qos].type << 2) | (aff * (uint32_t)p.n_req_terms << 4) |
-           (aff * (uint32_t)p.n_pref_terms << 8) | ((pod_honors(c, p) ? 1u : 0u) << 11) |
+           ((pod_honors_taints(c, p) ? 1u : 0u) << 7) | (aff * (uint32_t)p.n_pref_terms << 8) |
+           ((pod_honors_affinity(c, p) ? 1u : 0u) << 11) |
            ((soft || host ? 0u : (uint32_t)QS_AA_KIND(p.anti_affinity)) << 12) | ((soft ? 1u : 0u) << 14) |
            ((host ? 1u : 0u) << 15) | ((uint32_t)p.app << 16) | ((uint32_t)QS_AA_MAX_SKEW(p.anti_affinity) << 26);
 }
@@ -961,8 +973,10 @@ int pick_engine(const qs_ctx *c, uint32_t n, bool spread_over = false, bool host
         // nodeAffinityPolicy Honor (spec S16): the per-pod count pass over the nodes the pod's selector
         // admits exists on SCAN and the score path only
         if (honor && e == QS_ENGINE_PERSISTENT)
-            fail(QS_EINVAL, "PERSISTENT engine does not count topology spread under nodeAffinityPolicy Honor: a stream "
-                            "that holds a spread pod with a nodeSelector or required node-affinity terms runs SCAN");
+            fail(QS_EINVAL, "PERSISTENT engine does not count topology spread under nodeAffinityPolicy Honor or "
+                            "nodeTaintsPolicy Honor: a stream that holds a spread pod with a nodeSelector or required "
+                            "node-affinity terms (under nodeTaintsPolicy Honor: one that leaves a hard taint bit "
+                            "untolerated) runs SCAN");
         if (e == QS_ENGINE_AUTO)
             e = n <= persistent_max_nodes(feat) && !spread_over && !host_over && !honor ? QS_ENGINE_PERSISTENT
                                                                                          : QS_ENGINE_SCAN;
@@ -2062,6 +2076,26 @@ qs_status qs_get_topology_spread_node_affinity_policy(qs_ctx *c, int32_t *policy
     });
 }
 
+qs_status qs_set_topology_spread_node_taints_policy(qs_ctx *c, int32_t policy) {
+    return guarded(c, [&] {
+        if (!c->streams.empty())
+            fail(QS_ESTATE, "the topology spread nodeTaintsPolicy cannot change while prepared streams exist");
+        if (policy != QS_POLICY_IGNORE && policy != QS_POLICY_HONOR)
+            fail(QS_EINVAL, "the topology spread nodeTaintsPolicy must be QS_POLICY_IGNORE or QS_POLICY_HONOR");
+        if (policy == QS_POLICY_HONOR && !c->cfg.enable_taint)
+            fail(QS_EINVAL, "QS_POLICY_HONOR needs the TaintToleration filter (config.enable_taint = 1): it counts "
+                            "the nodes that filter admits");
+        c->taints_policy = policy;
+    });
+}
+
+qs_status qs_get_topology_spread_node_taints_policy(qs_ctx *c, int32_t *policy) {
+    return guarded(c, [&] {
+        if (!policy) fail(QS_EINVAL, "null output");
+        *policy = c->taints_policy;
+    });
+}
+
 qs_status qs_score_pod_zone_scores(qs_ctx *c, int32_t *out) {
     return guarded(c, [&] {
         if (!out) fail(QS_EINVAL, "null output");
@@ -2158,7 +2192,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         check_row_values(one, 0);
         if (c->hcount.p && r->max_pods > kHcMaxPods)
             fail(QS_EINVAL, "max_pods above 65535 on a context that counts pods per (app, node) in 16 bits "
-                            "(QS_AA_SPREAD_HOSTNAME, spec S15; nodeAffinityPolicy Honor, spec S16)");
+                            "(QS_AA_SPREAD_HOSTNAME, spec S15; nodeAffinityPolicy / nodeTaintsPolicy Honor, spec S16 / S17)");
         if (c->aa_track && idx < m.n && r->zone != m.zone[idx] && m.aa_holds(idx))
             fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
                             "cannot change while tracking is on");

@@ -185,8 +185,9 @@ __device__ __forceinline__ const uint8_t *soft_zone_bytes(const DevTable &t, uin
 // The minimum travels inverted, kHsInv - cnt >= 1 per real node, so that it is a maximum, 0 is the
 // neutral element of idle lanes and of the reset word, and the DPP wave maximum serves.
 constexpr uint32_t kHsInv = 0x10000u;
-// pod-flag bit 7 (free in the record): set by the score path's launcher in its by-value copy of the pod
-// for the launch of k_score_podg_max that takes the minimum and nothing else
+// pod-flag bit 7: set by the score path's launcher in its by-value copy of the pod for the launch of
+// k_score_podg_max that takes the minimum and nothing else.  (The records of the normalizing kFeatAA
+// classes carry bit 7 themselves, spec S17, and mark that launch in bit 31: kHsMinMark below.)
 constexpr uint32_t kHsMinPass = 1u << 7;
 __host__ __device__ __forceinline__ bool pod_hostspread(uint32_t flags) { return ((flags >> 15) & 1u) != 0; }
 __device__ __forceinline__ uint16_t *aa_hcount(const DevTable &t) {
@@ -222,23 +223,40 @@ constexpr uint32_t kHonorBit = 1u << 11;
 // 31 of the score path's by-value copy of the pod (the batched claim's bit in its own staged copies, free
 // here; bit 7 is the hostname minimum's)
 constexpr uint32_t kHonorScanPass = 0x40000000u, kHonorCntPass = 1u << 31;
+// nodeTaintsPolicy Honor (spec S17).  Pod-record bit 7, resolved on the host: the context's policy is HONOR
+// and the pod is a spread pod of any of the three kinds that leaves a hard taint bit untolerated.  M(pod) is
+// then M_A ∩ M_T, M_A under bit 11 (all nodes without it) and M_T = the nodes that pass the TaintToleration
+// filter's predicate under bit 7 (all nodes without it): the second inclusion predicate of honor_match, from
+// the mask row every caller has already loaded.  Everything else of S16 reads pod_honor, either bit.
+// In these classes the score path's launcher therefore cannot mark the hostname minimum's launch in bit 7 of
+// its copy (kHsMinPass): bit 31 marks both launches, the minimum's for a hostname-spread pod and the count
+// pass for every other pod (a pod gets one of the two, never both).
+constexpr uint32_t kTaintHonorBit = 1u << 7;
 template <uint32_t F>
 constexpr bool kHonorF = (F & kFeatAA) != 0 && (F & kFeatAffinity) != 0;
-__host__ __device__ __forceinline__ bool pod_honor(uint32_t flags) { return (flags & kHonorBit) != 0; }
-// i in M(pod): the kFeatAffinity part of feasible<F> on its own
+__host__ __device__ __forceinline__ bool pod_honor(uint32_t flags) {
+    return (flags & (kHonorBit | kTaintHonorBit)) != 0;
+}
+// the mark of the hostname minimum's launch in the score path's copy of the pod (host and device)
+template <uint32_t F>
+constexpr uint32_t kHsMinMark = kHonorF<F> ? kHonorCntPass : kHsMinPass;
+// i in M(pod): the kFeatAffinity part of feasible<F> on its own under bit 11, the kFeatTaint part under bit 7
 template <class P>
 __device__ __forceinline__ bool honor_match(const RowX &x, const P &p, const DPodX &px) {
     bool ok = true;
-    const uint64_t s0 = uniform64(px.sel0), s1 = uniform64(px.sel1);
-    if (s0 | s1) ok &= subset128(s0, s1, x.lb0, x.lb1);
-    const uint32_t nt = (uint32_t)__builtin_amdgcn_readfirstlane((int)((p.flags >> 4) & 7u));
-    if (nt != 0) {
-        bool any = false;
+    if ((p.flags & kHonorBit) != 0) {  // (wave-uniform)
+        const uint64_t s0 = uniform64(px.sel0), s1 = uniform64(px.sel1);
+        if (s0 | s1) ok &= subset128(s0, s1, x.lb0, x.lb1);
+        const uint32_t nt = (uint32_t)__builtin_amdgcn_readfirstlane((int)((p.flags >> 4) & 7u));
+        if (nt != 0) {
+            bool any = false;
 #pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (k < nt) any |= subset128(px.req[k][0], px.req[k][1], x.lb0, x.lb1);
-        ok &= any;
+            for (uint32_t k = 0; k < 4; ++k)
+                if (k < nt) any |= subset128(px.req[k][0], px.req[k][1], x.lb0, x.lb1);
+            ok &= any;
+        }
     }
+    if ((p.flags & kTaintHonorBit) != 0) ok &= (x.th & ~px.tol_hard) == 0;  // UP tainttoleration#Filter
     return ok;
 }
 // The count pass of one workgroup of NW waves; every thread calls it (two barriers).  `nodes(visit)` runs
@@ -1129,8 +1147,9 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     [[maybe_unused]] bool minpass = false, honor = false;
     if constexpr (kHonorF<F>) {
         // the count pass of nodeAffinityPolicy Honor (spec S16; kHonorCntPass in the launcher's copy of the
-        // pod, workgroup-uniform): the sums and the domains over M(pod) into the words behind gs[5]
-        if ((p.flags & kHonorCntPass) != 0) {
+        // pod, workgroup-uniform): the sums and the domains over M(pod) into the words behind gs[5].  (On a
+        // hostname-spread pod the same bit marks the minimum's launch: kHsMinMark, spec S17.)
+        if ((p.flags & kHonorCntPass) != 0 && !pod_hostspread(p.flags)) {
             const uint16_t *h = aa_hcount(t);
             honor_count<kScorePodGT / kWave>(h ? h + (size_t)pod_app(p.flags) * t.cap : nullptr,
                                              reinterpret_cast<uint32_t *>(gs + kGsCnt), gs + kGsDom, [&](auto &&visit) {
@@ -1149,7 +1168,7 @@ __global__ __launch_bounds__(kScorePodGT) void k_score_podg_max(DevTable t, PodT
     if constexpr ((F & kFeatAA) != 0) {
         zw = spread_word_h<F>(t, p.flags, reinterpret_cast<const uint32_t *>(gs + kGsCnt), gs + kGsDom);
         hc = hs_row(t, p.flags);
-        minpass = (p.flags & kHsMinPass) != 0;
+        minpass = (p.flags & kHsMinMark<F>) != 0;
         if (hc && !minpass) hm = (uint32_t)__hip_atomic_load(gs + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (i < n) {
@@ -5253,7 +5272,7 @@ static hipError_t score_pod1_f(const DevTable &t, const void *pod, const DPodX *
             // a hostname-spread pod (spec S15): first the minimum of its app's node counts, alone
             if (pod_hostspread(p.flags)) {
                 PodT<F> pm = p;
-                pm.flags |= kHsMinPass;
+                pm.flags |= kHsMinMark<F>;  // (bit 7; bit 31 in the classes whose records carry bit 7, spec S17)
                 hipLaunchKernelGGL((k_score_podg_max<F>), dim3(g), dim3(kScorePodGT), 0, stream, t, pm, px, gs, pidx,
                                    prow);
             }

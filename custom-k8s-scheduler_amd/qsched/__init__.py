@@ -268,6 +268,18 @@ class Scheduler:
         self._chk(self.lib.qs_get_topology_spread_node_affinity_policy(self.ctx, ctypes.byref(v)))
         return int(v.value)
 
+    def set_topology_spread_node_taints_policy(self, policy):
+        """qs_set_topology_spread_node_taints_policy: "ignore" / "honor" (or QS_POLICY_*), spec S17.  Under
+        "honor" a spread pod counts, and takes its domains from, the nodes whose hard taints it tolerates
+        only (needs enable_taint = 1); "ignore" in a new context."""
+        pol = POLICIES[policy] if isinstance(policy, str) else int(policy)
+        self._chk(self.lib.qs_set_topology_spread_node_taints_policy(self.ctx, pol))
+
+    def get_topology_spread_node_taints_policy(self) -> int:
+        v = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_topology_spread_node_taints_policy(self.ctx, ctypes.byref(v)))
+        return int(v.value)
+
     def score_pod_zone_scores(self):
         """qs_score_pod_zone_scores: int32[QS_MAX_ZONES], the PodTopologySpread score per zone of the last
         score_pod / score_pod_packed call (-1: no feasible node there, or no soft-spread pod)."""

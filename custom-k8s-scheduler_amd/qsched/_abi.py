@@ -25,7 +25,7 @@ QS_AA_NONE, QS_AA_HOSTNAME, QS_AA_ZONE = 0, 1, 2
 QS_AA_SPREAD_ZONE, QS_MAX_SPREAD_SKEW = 3, 31  # spec S13: kind in the low byte, max_skew in bits 8-12
 QS_AA_SOFT = 1 << 16  # spec S14: ScheduleAnyway, with QS_AA_SPREAD_ZONE only
 QS_AA_HOSTKEY = 1 << 18  # spec S15: the spread key is the node, with QS_AA_SPREAD_ZONE only and without QS_AA_SOFT
-QS_POLICY_IGNORE, QS_POLICY_HONOR = 0, 1  # spec S16: nodeAffinityPolicy of the context's spread constraints
+QS_POLICY_IGNORE, QS_POLICY_HONOR = 0, 1  # spec S16 / S17: nodeAffinityPolicy / nodeTaintsPolicy of the context's spread constraints
 QS_MAX_SCORE_RES = 4
 # qs_fit_reason: FitError reason columns of qs_stream_fit_errors, with upstream's reason strings
 FIT_REASONS = ["Too many pods", "Insufficient cpu", "Insufficient memory", "Insufficient {ext0}",
@@ -161,6 +161,8 @@ _SIGS = {
     "qs_get_topology_spread_weight": (ctypes.c_int, [_P, _P]),
     "qs_set_topology_spread_node_affinity_policy": (ctypes.c_int, [_P, ctypes.c_int32]),
     "qs_get_topology_spread_node_affinity_policy": (ctypes.c_int, [_P, _P]),
+    "qs_set_topology_spread_node_taints_policy": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "qs_get_topology_spread_node_taints_policy": (ctypes.c_int, [_P, _P]),
     "qs_score_pod_zone_scores": (ctypes.c_int, [_P, _P]),
     "qs_shape_table": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "qs_close": (ctypes.c_int, [_P]),

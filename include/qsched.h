@@ -75,7 +75,8 @@ typedef enum qs_mode { QS_MODE_EXACT = 0, QS_MODE_BATCHED = 1 } qs_mode;
  * context that tracks it (qs_set_pod_anti_affinity, spec S12) and ignore it otherwise.
  * QS_AA_SPREAD_ZONE (spec S13) is the zone topologySpreadConstraint with whenUnsatisfiable:
  * DoNotSchedule over the pod's own app (UP plugins/podtopologyspread Filter; nodeAffinityPolicy Ignore
- * unless qs_set_topology_spread_node_affinity_policy says HONOR (spec S16), nodeTaintsPolicy Ignore,
+ * unless qs_set_topology_spread_node_affinity_policy says HONOR (spec S16), nodeTaintsPolicy Ignore
+ * unless qs_set_topology_spread_node_taints_policy says HONOR (spec S17),
  * minDomains unset): a node is infeasible when taking it would leave its zone
  * more than max_skew pods of the app above the emptiest zone that holds a node of the table.  The kind
  * sits in the low byte of qs_pod.anti_affinity and max_skew (1..31) in bits 8-12: QS_AA_SPREAD(max_skew).
@@ -368,6 +369,24 @@ QS_API qs_status qs_get_topology_spread_weight(qs_ctx *ctx, int32_t *w);
 typedef enum qs_node_inclusion_policy { QS_POLICY_IGNORE = 0, QS_POLICY_HONOR = 1 } qs_node_inclusion_policy;
 QS_API qs_status qs_set_topology_spread_node_affinity_policy(qs_ctx *ctx, int32_t policy);
 QS_API qs_status qs_get_topology_spread_node_affinity_policy(qs_ctx *ctx, int32_t *policy);
+/* nodeTaintsPolicy of the context's topology spread constraints (spec S17; UP
+ * apis/core#TopologySpreadConstraint.NodeTaintsPolicy, KEP-3094,
+ * podtopologyspread/common.go#matchNodeInclusionPolicies, which calls FindMatchingUntoleratedTaint with
+ * DoNotScheduleTaintsFilterFunc: NoSchedule and NoExecute taints).  QS_POLICY_IGNORE (a new context, and
+ * upstream's default for this field; spec S13-S16 to the letter): tainted nodes count like any other.
+ * QS_POLICY_HONOR: for a spread pod, only the nodes whose hard taints it tolerates (taint_hard & ~tol_hard
+ * == 0, the TaintToleration filter's predicate) are counted and make up the domains of QS_AA_SPREAD,
+ * QS_AA_SPREAD_SOFT and QS_AA_SPREAD_HOSTNAME pods.  Under both policies the node set is the intersection
+ * of the two.  A tainted pool that a Deployment cannot use then no longer pins the minimum of its spread
+ * at 0.  Like the affinity policy it is per context, and read on a context that tracks pod anti-affinity
+ * only.  A pod restricts by taints when ~tol_hard != 0; a stream that holds such a spread pod under HONOR
+ * runs QS_ENGINE_SCAN (AUTO picks it; an explicit QS_ENGINE_PERSISTENT returns QS_EINVAL) and the context
+ * keeps the per-(app, node) counts with their limits, as under the affinity policy; a pod that tolerates
+ * every bit is dispatched as before.  QS_ESTATE while the context holds prepared streams; QS_EINVAL for an
+ * unknown policy, a null pointer, a null context, and for HONOR on a context opened with enable_taint = 0
+ * (Honor presupposes that the TaintToleration filter removes the nodes outside the set). */
+QS_API qs_status qs_set_topology_spread_node_taints_policy(qs_ctx *ctx, int32_t policy);
+QS_API qs_status qs_get_topology_spread_node_taints_policy(qs_ctx *ctx, int32_t *policy);
 QS_API qs_status qs_close(qs_ctx *ctx);
 QS_API const char *qs_last_error(const qs_ctx *ctx);
 QS_API const char *qs_version(void);

@@ -21,6 +21,11 @@ Arms per table:
                     nodeAffinityPolicy Honor (spec S16, DESIGN.md §3.8), checked against tests/honor_spread_ref.py;
   ignore_*_scan     the same three streams under the policy Ignore: honor_* against ignore_* is the cost of
                     the count pass (one more launch per restricting SPREAD / SPREAD_SOFT pod; none for hostname)
+  taint_honor_spread_scan      the spread_scan / soft_scan / hostspread_scan streams with the TaintToleration filter
+  taint_honor_soft_scan        on (enable_taint = 1: the normalizing class), the nodes of zones 2 and 3 tainted, the
+  taint_honor_hostspread_scan  pods of the converted kind tolerating nothing and every other pod everything, under
+                    nodeTaintsPolicy Honor (spec S17, DESIGN.md §3.9), checked against tests/taint_spread_ref.py;
+  taint_ignore_*_scan  the same three streams under the policy Ignore
   plain_persistent  the same table and pods with tracking off (placements ignore anti-affinity):
   plain_scan        the cost of the filter and the recording is aa_* against plain_*
 
@@ -40,7 +45,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARMS = ["batched1", "aa_persistent", "aa_scan", "spread_persistent", "spread_scan", "soft_persistent", "soft_scan",
         "hostspread_persistent", "hostspread_scan", "honor_spread_scan", "honor_soft_scan", "honor_hostspread_scan",
-        "ignore_spread_scan", "ignore_soft_scan", "ignore_hostspread_scan", "plain_persistent", "plain_scan"]
+        "ignore_spread_scan", "ignore_soft_scan", "ignore_hostspread_scan", "taint_honor_spread_scan",
+        "taint_honor_soft_scan", "taint_honor_hostspread_scan", "taint_ignore_spread_scan", "taint_ignore_soft_scan",
+        "taint_ignore_hostspread_scan", "plain_persistent", "plain_scan"]
 
 
 def paths(tree):
@@ -59,9 +66,12 @@ def run_arm(n, p, arm, steps, prefix):
     nodes, pods = synth_generate(5, n, p)
     nodes, pods = A.fold(nodes, pods, 40, 4)
     policy = None  # honor_* / ignore_*: the arm behind the prefix with a selector on its spread pods
+    taints = arm.startswith("taint_")  # taint_honor_* / taint_ignore_*: ... with a tainted half of the table
+    if taints:
+        arm = arm[len("taint_"):]
     if arm.startswith(("honor_", "ignore_")):
         policy, arm = arm.split("_", 1)
-        out_arm = policy + "_" + arm
+        out_arm = ("taint_" if taints else "") + policy + "_" + arm
     else:
         out_arm = arm
     soft = arm.startswith("soft_")
@@ -88,7 +98,15 @@ def run_arm(n, p, arm, steps, prefix):
     cfg = dict(engine=engine, batch_pods=1) if batched else dict(engine=engine)
     mode = "batched" if batched else "exact"
     out = dict(nodes=n, pods=p, arm=out_arm)
-    if policy:
+    if taints:
+        import taint_spread_ref as TR
+
+        nodes = {k: v.copy() for k, v in nodes.items()}
+        nodes["taint_hard"][nodes["zone"] >= 2] = np.uint64(1 << 8)
+        pods = pods.copy()
+        pods["tol_hard"] = np.where((pods["anti_affinity"] & 0xFF) == 3, np.uint64(0), ~np.uint64(0))
+        cfg["enable_taint"] = 1
+    elif policy:
         import honor_spread_ref as HR
 
         nodes = {k: v.copy() for k, v in nodes.items()}
@@ -99,7 +117,12 @@ def run_arm(n, p, arm, steps, prefix):
     with Scheduler(cfg) as s:
         if tracked:
             s.set_pod_anti_affinity(True)
-        if policy:
+        if taints:
+            if not hasattr(s, "set_topology_spread_node_taints_policy"):  # (--tree: a tree from before S17)
+                out.update(skipped="no qs_set_topology_spread_node_taints_policy in this tree")
+                return out
+            s.set_topology_spread_node_taints_policy(policy)
+        elif policy:
             if not hasattr(s, "set_topology_spread_node_affinity_policy"):  # (--tree: a tree from before S16)
                 out.update(skipped="no qs_set_topology_spread_node_affinity_policy in this tree")
                 return out
@@ -119,7 +142,10 @@ def run_arm(n, p, arm, steps, prefix):
             return out
         pl, keys = head.results()
         head.free()
-        if policy:
+        if taints:
+            ref = TR.run(nodes, pods[:prefix], dict(enable_taint=1),
+                         taints_policy=TR.HONOR if policy == "honor" else TR.IGNORE)
+        elif policy:
             ref = HR.run(nodes, pods[:prefix], dict(enable_affinity=1),
                          policy=HR.HONOR if policy == "honor" else HR.IGNORE)
         elif host:
@@ -184,10 +210,10 @@ def main():
             if r["nodes"] != n:
                 continue
             if "skipped" in r:
-                print(f"n {n:5d} {r['arm']:22s} skipped: {r['skipped'][:90]}")
+                print(f"n {n:5d} {r['arm']:28s} skipped: {r['skipped'][:90]}")
                 continue
             rel = f"x{r['us_per_pod'] / base['us_per_pod']:.3f} of batched1" if base else ""
-            print(f"n {n:5d} {r['arm']:22s} {r['ms_per_step']:10.3f} ms  {r['us_per_pod']:8.3f} us/pod  {rel}  "
+            print(f"n {n:5d} {r['arm']:28s} {r['ms_per_step']:10.3f} ms  {r['us_per_pod']:8.3f} us/pod  {rel}  "
                   f"engine {r['engine_used']}  prefix {'ok' if r['prefix_ok'] else 'DIFFERS'}")
     return 1 if bad else 0
 
