@@ -28,6 +28,8 @@ constexpr uint32_t kSoaMinNodes = 1u << 16;
 // Tables up to this size also keep the batched-mode anti-affinity state (128 B of app bits per
 // node + the (app, zone) counts) inside the table allocation, so save/restore covers it.
 constexpr uint32_t kAaMaxNodes = 1u << 20;
+// Tables up to this size may keep the pod registry (spec S18): its device copy is slots x cap x 48 bytes.
+constexpr uint32_t kRegMaxNodes = 1u << 17;
 
 struct QsError {
     qs_status st;
@@ -69,9 +71,22 @@ struct DevBuf {
     T *as() const { return (T *)p; }
 };
 
+// One pod on a node (the pod registry of spec S18): its importance under the context's policy, its
+// sequence number and what Reserve added for it.
+struct RegEntry {
+    uint64_t imp, seq;
+    int64_t rc, rm, re[QS_MAX_EXT], zc, zm;
+    int32_t priority, qos, app;
+};
+
 // Host mirror of the canonical table.
 struct Mirror {
     uint32_t n = 0;
+    // The pod registry (spec S18; authoritative, the device copy qs_ctx::reg_dev is derived): one list per
+    // node, sorted by (imp descending, seq ascending), empty until the registry is switched on, and the
+    // context-wide sequence counter.  Part of the mirror, so qs_table_save / qs_table_restore carry both.
+    std::vector<std::vector<RegEntry>> reg;
+    uint64_t reg_seq = 0;
     std::vector<int64_t> ac, am, mp, rc, rm, zc, zm, np;
     std::vector<int64_t> ae, re;  // [n][QS_MAX_EXT]
     std::vector<uint64_t> th, ts, lb;  // lb [n][2]
@@ -220,6 +235,18 @@ struct qs_ctx {
     int32_t spread_policy = 0;
     // nodeTaintsPolicy likewise (qs_set_topology_spread_node_taints_policy, spec S17): resolved into bit 7
     int32_t taints_policy = 0;
+    // Preemption (spec S18): the registry switch and the importance policy, and the device
+    // copy of Mirror::reg (kRegCols columns of reg_slots x reg_cap u64, slot-major, then reg_cap lengths).
+    // reg_all says that the whole copy is stale (a switch of policy, a load, a restore, a device fault, a
+    // reallocation); otherwise the nodes of reg_dirty are (reg_mark: 1 = listed).  reg_long = nodes whose
+    // list is longer than QS_MAX_VICTIMS (qs_preempt_pod refuses while there is one).
+    bool preempt_on = false;
+    int32_t preempt_policy = 0;
+    qs_host::DevBuf reg_dev, reg_stage, reg_out, reg_nv, reg_rec;
+    uint32_t reg_slots = 0, reg_cap = 0, reg_long = 0;
+    bool reg_all = true;
+    std::vector<uint32_t> reg_dirty;
+    std::vector<uint8_t> reg_mark;
     std::vector<qs_stream *> streams;  // prepared and not yet freed (qs_close detaches them)
     qs_host::DevBuf tbl;  // all columns in one allocation
     qs_host::DevBuf soa;  // SoA int32 copy (kSCols x cap) when n >= soa_min_nodes

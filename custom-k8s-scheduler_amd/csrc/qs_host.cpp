@@ -556,6 +556,7 @@ void upload_table(qs_ctx *c) {
         HIPCHK(hipMemcpyAsync(c->soa.p, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->reg_all = true;  // the registry's device copy is rebuilt with the table (spec S18)
     c->dev_valid = true;
     c->soa_valid = soa;
     c->mirror_stale = false;
@@ -774,6 +775,162 @@ void mirror_reserve(Mirror &m, uint32_t i, const qs_pod &p, int sign) {
     m.zc[i] += sign * p.nz_cpu;
     m.zm[i] += sign * p.nz_mem;
     m.np[i] += sign;
+}
+
+// ---- pod registry (spec S18) ------------------------------------------------------
+// Importance of a pod under the context's policy, as an unsigned 64-bit value.
+uint64_t reg_importance(int32_t policy, int32_t qos, int32_t priority) {
+    const uint64_t base = (uint64_t)((int64_t)priority + (1LL << 31));
+    return policy == QS_PREEMPT_BY_QOS ? ((uint64_t)(uint32_t)qos << 32) + base : base;
+}
+bool reg_more_important(const RegEntry &a, const RegEntry &b) {  // UP util.MoreImportantPod
+    return a.imp != b.imp ? a.imp > b.imp : a.seq < b.seq;
+}
+// The device copy of node's list is stale.
+void reg_touch(qs_ctx *c, uint32_t node) {
+    if (c->reg_all) return;
+    if (c->reg_mark.size() < c->m.n) c->reg_mark.resize(c->m.n, 0);
+    if (node < c->reg_mark.size() && !c->reg_mark[node]) {
+        c->reg_mark[node] = 1;
+        c->reg_dirty.push_back(node);
+    }
+}
+// ... of every node is (and the count of over-long lists is taken again)
+void reg_stale(qs_ctx *c) {
+    c->reg_all = true;
+    c->reg_dirty.clear();
+    c->reg_mark.clear();
+    c->reg_long = 0;
+    for (const auto &l : c->m.reg) c->reg_long += l.size() > QS_MAX_VICTIMS ? 1u : 0u;
+}
+// Every entry's importance under the context's policy and every list in its walk order again.
+void reg_resort(qs_ctx *c) {
+    for (auto &l : c->m.reg) {
+        for (RegEntry &e : l) e.imp = reg_importance(c->preempt_policy, e.qos, e.priority);
+        std::sort(l.begin(), l.end(), reg_more_important);
+    }
+    reg_stale(c);
+}
+std::vector<RegEntry> &reg_list(qs_ctx *c, uint32_t node) {
+    if (c->m.reg.size() < c->m.n) c->m.reg.resize(c->m.n);
+    return c->m.reg[node];
+}
+bool reg_holds(const qs_ctx *c, uint32_t node) { return node < c->m.reg.size() && !c->m.reg[node].empty(); }
+void reg_append(qs_ctx *c, uint32_t node, const qs_pod &p) {
+    auto &l = reg_list(c, node);
+    RegEntry e{reg_importance(c->preempt_policy, p.qos, p.priority), ++c->m.reg_seq, p.req_cpu, p.req_mem, {},
+               p.nz_cpu, p.nz_mem, p.priority, p.qos, p.app};
+    for (int k = 0; k < QS_MAX_EXT; k++) e.re[k] = p.req_ext[k];
+    // behind every entry at least as important (the new entry carries the highest seq)
+    const auto it = std::upper_bound(l.begin(), l.end(), e, [](const RegEntry &a, const RegEntry &b) { return a.imp > b.imp; });
+    l.insert(it, e);
+    if (l.size() == (size_t)QS_MAX_VICTIMS + 1) ++c->reg_long;
+    reg_touch(c, node);
+}
+void reg_erase(qs_ctx *c, uint32_t node, size_t at) {
+    auto &l = reg_list(c, node);
+    if (l.size() == (size_t)QS_MAX_VICTIMS + 1) --c->reg_long;
+    l.erase(l.begin() + (ptrdiff_t)at);
+    reg_touch(c, node);
+}
+// The entry of `node` with the highest seq whose fields equal the pod's (qs_unreserve), or the entry `seq`
+// (qs_evict, seq != 0); -1: none.
+ptrdiff_t reg_find(const qs_ctx *c, uint32_t node, const qs_pod *p, uint64_t seq) {
+    if (node >= c->m.reg.size()) return -1;
+    const auto &l = c->m.reg[node];
+    ptrdiff_t at = -1;
+    for (size_t k = 0; k < l.size(); k++) {
+        const RegEntry &e = l[k];
+        if (seq != 0) {
+            if (e.seq == seq) return (ptrdiff_t)k;
+            continue;
+        }
+        if (e.priority == p->priority && e.qos == p->qos && e.app == p->app && e.rc == p->req_cpu && e.rm == p->req_mem &&
+            e.re[0] == p->req_ext[0] && e.re[1] == p->req_ext[1] && e.zc == p->nz_cpu && e.zm == p->nz_mem &&
+            (at < 0 || e.seq > l[(size_t)at].seq))
+            at = (ptrdiff_t)k;
+    }
+    return at;
+}
+qs_victim reg_victim(const RegEntry &e) {
+    qs_victim v{};
+    v.seq = e.seq;
+    v.req_cpu = e.rc; v.req_mem = e.rm; v.nz_cpu = e.zc; v.nz_mem = e.zm;
+    for (int k = 0; k < QS_MAX_EXT; k++) v.req_ext[k] = e.re[k];
+    v.priority = e.priority; v.qos = e.qos; v.app = e.app;
+    return v;
+}
+// A qs_node_upsert of a node that holds entries: the row may not claim less than they add up to.
+void reg_check_row(const qs_ctx *c, uint32_t node, const qs_node_row &r) {
+    int64_t rc = 0, rm = 0, zc = 0, zm = 0, re[QS_MAX_EXT] = {};
+    const auto &l = c->m.reg[node];
+    for (const RegEntry &e : l) {
+        rc += e.rc; rm += e.rm; zc += e.zc; zm += e.zm;
+        for (int k = 0; k < QS_MAX_EXT; k++) re[k] += e.re[k];
+    }
+    bool ok = r.req_cpu >= rc && r.req_mem >= rm && r.nz_cpu >= zc && r.nz_mem >= zm && r.pods >= (int64_t)l.size();
+    for (int k = 0; k < QS_MAX_EXT; k++) ok = ok && r.req_ext[k] >= re[k];
+    if (!ok)
+        fail(QS_EINVAL, "node " + std::to_string(node) + ": the row's requested columns or pod count fall below the "
+                        "sums over its " + std::to_string(l.size()) + " registered pods (spec S18)");
+}
+// The device copy brought up to date: the dirty nodes' columns through one staging copy and one scatter
+// launch, or every node's after reg_stale / a reallocation.  slots = the longest list rounded up to a
+// power of two, 8..QS_MAX_VICTIMS; growth reallocates.
+void reg_sync_device(qs_ctx *c) {
+    const uint32_t n = c->m.n, cap = c->cap;
+    if (c->m.reg.size() < n) c->m.reg.resize(n);
+    if (cap != c->reg_cap || !c->reg_dev.p) c->reg_all = true;
+    // few dirty nodes: their columns; many: the whole copy (one pass, no marks to keep)
+    if (!c->reg_all && (size_t)c->reg_dirty.size() * 4 > n) reg_stale(c);
+    size_t longest = 0;
+    if (c->reg_all) for (uint32_t i = 0; i < n; i++) longest = std::max(longest, c->m.reg[i].size());
+    else for (uint32_t i : c->reg_dirty) if (i < n) longest = std::max(longest, c->m.reg[i].size());
+    uint32_t slots = 8;
+    while (slots < longest && slots < QS_MAX_VICTIMS) slots <<= 1;
+    // growth: a new extent, every node again (no other list is longer than the old extent, so `slots` stands)
+    if (!c->reg_all && slots > c->reg_slots) c->reg_all = true;
+    if (c->reg_all) {
+        c->reg_dev.ensure((size_t)kRegCols * slots * cap * 8 + (size_t)cap * 4);
+        c->reg_slots = slots;
+        c->reg_cap = cap;
+        c->reg_dirty.clear();
+        c->reg_mark.clear();
+    }
+    uint64_t *col = c->reg_dev.as<uint64_t>();
+    uint32_t *len = reinterpret_cast<uint32_t *>(col + (size_t)kRegCols * c->reg_slots * cap);
+    std::vector<RegItem> items;
+    std::vector<uint32_t> lnode, lval;
+    auto add = [&](uint32_t i) {
+        const auto &l = c->m.reg[i];
+        lnode.push_back(i);
+        lval.push_back((uint32_t)std::min<size_t>(l.size(), c->reg_slots));
+        for (uint32_t s = 0; s < l.size() && s < c->reg_slots; s++) {
+            const RegEntry &e = l[s];
+            items.push_back(RegItem{i, s, {e.imp, e.seq, (uint64_t)e.rc, (uint64_t)e.rm, (uint64_t)e.re[0], (uint64_t)e.re[1]}});
+        }
+    };
+    if (c->reg_all) {
+        if (cap) HIPCHK(hipMemsetAsync(len, 0, (size_t)cap * 4, c->stream));
+        for (uint32_t i = 0; i < n; i++) if (!c->m.reg[i].empty()) add(i);
+    } else {
+        for (uint32_t i : c->reg_dirty) if (i < n) add(i);
+    }
+    if (!lnode.empty()) {
+        const size_t ib = items.size() * sizeof(RegItem), lb = lnode.size() * 4;
+        c->reg_stage.ensure(ib + 2 * lb + 16);
+        char *st = c->reg_stage.as<char>();
+        if (ib) HIPCHK(hipMemcpyAsync(st, items.data(), ib, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(st + ib, lnode.data(), lb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(st + ib + lb, lval.data(), lb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(launch_preempt_scatter(col, len, c->reg_slots, cap, reinterpret_cast<const RegItem *>(st),
+                                      (uint32_t)items.size(), reinterpret_cast<const uint32_t *>(st + ib),
+                                      reinterpret_cast<const uint32_t *>(st + ib + lb), (uint32_t)lnode.size(), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));  // (the staging vectors leave scope)
+    }
+    for (uint32_t i : c->reg_dirty) if (i < c->reg_mark.size()) c->reg_mark[i] = 0;
+    c->reg_dirty.clear();
+    c->reg_all = false;
 }
 
 // Device layout for the mirror plus the pods about to be scored (spec S10):
@@ -1797,14 +1954,18 @@ void finish_run(qs_ctx *c, qs_stream *s, qs_mode mode, const RunPlan &plan, cons
     // keep the host mirror authoritative after every stream (one D2H of the rows, outside
     // the timed region): a later device fault rebuilds the table from it
     sync_mirror(c);
-    if (c->aa_track && P > 0 && n > 0) {
+    if ((c->aa_track || c->preempt_on) && P > 0 && n > 0) {
         // fold the run's placements into the mirror's anti-affinity state (4 P bytes back, outside
-        // wall_s): the mirror stays authoritative for save / restore and the recovery rebuild
+        // wall_s): the mirror stays authoritative for save / restore and the recovery rebuild;
+        // ... and into the pod registry (spec S18), in the stream's decision order
         std::vector<int32_t> node(P);
         HIPCHK(hipMemcpy(node.data(), s->d_node.p, 4 * (size_t)P, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < P; k++)
-            if (node[k] >= 0 && (uint32_t)node[k] < n)
-                c->m.aa_add((uint32_t)s->pods[s->order[k]].app, (uint32_t)node[k], +1);
+        for (uint32_t k = 0; k < P; k++) {
+            if (node[k] < 0 || (uint32_t)node[k] >= n) continue;
+            const qs_pod &pod = s->pods[s->order[k]];
+            if (c->aa_track) c->m.aa_add((uint32_t)pod.app, (uint32_t)node[k], +1);
+            if (c->preempt_on) reg_append(c, (uint32_t)node[k], pod);
+        }
     }
     s->aa_ran = plan.aa_exact;
     s->ran = true;
@@ -2117,6 +2278,8 @@ qs_status qs_nodes_load(qs_ctx *c, const qs_node_soa *nd, uint32_t n) {
         Mirror &m = c->m;
         m.resize(n);
         m.aa_clear();  // no pod recorded on a new table (spec S12)
+        m.reg.clear();  // ... and none registered (spec S18; the sequence counter runs on)
+        reg_stale(c);
         auto get = [](const int64_t *a, size_t i, int64_t d) { return a ? a[i] : d; };
         for (uint32_t i = 0; i < n; i++) {
             m.ac[i] = nd->alloc_cpu[i];
@@ -2196,6 +2359,7 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
         if (c->aa_track && idx < m.n && r->zone != m.zone[idx] && m.aa_holds(idx))
             fail(QS_EINVAL, "node " + std::to_string(idx) + " holds pods recorded for anti-affinity: its zone "
                             "cannot change while tracking is on");
+        if (reg_holds(c, idx)) reg_check_row(c, idx, *r);
         const bool was_zero = idx < m.n && zero_alloc_row(m, idx);
         const bool zone_moves = idx < m.n && r->zone != m.zone[idx];  // (an append re-uploads the table)
         if (idx == m.n) {  // append one node
@@ -2203,9 +2367,12 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
             auto aa_node = std::move(m.aa_node);
             auto aa_zone = std::move(m.aa_zone);
             auto aa_pods = std::move(m.aa_pods);
+            auto reg = std::move(m.reg);  // (the registry likewise, spec S18)
             m.aa_clear();
+            m.reg.clear();
             Mirror old = m;
             m.resize(old.n + 1);
+            m.reg = std::move(reg);
             m.aa_node = std::move(aa_node);
             m.aa_zone = std::move(aa_zone);
             m.aa_pods = std::move(aa_pods);
@@ -2238,8 +2405,23 @@ qs_status qs_node_upsert(qs_ctx *c, uint32_t idx, const qs_node_row *r, uint64_t
     });
 }
 
-static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sign) {
+// evict_seq != 0 (qs_evict, spec S18): an Unreserve of the registry entry with that sequence number, the pod
+// rebuilt from the entry; 0: the pod is the caller's.
+static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sign, uint64_t evict_seq = 0) {
+    qs_pod from_entry;
     return guarded(c, [&] {
+        ptrdiff_t reg_at = -1;
+        if (evict_seq != 0) {
+            reg_at = node < c->m.n ? reg_find(c, node, nullptr, evict_seq) : -1;
+            if (reg_at < 0)
+                fail(QS_EINVAL, "qs_evict: node " + std::to_string(node) + " holds no entry with seq " + std::to_string(evict_seq));
+            const RegEntry &e = c->m.reg[node][(size_t)reg_at];
+            std::memset(&from_entry, 0, sizeof from_entry);
+            from_entry.req_cpu = e.rc; from_entry.req_mem = e.rm; from_entry.nz_cpu = e.zc; from_entry.nz_mem = e.zm;
+            for (int k = 0; k < QS_MAX_EXT; k++) from_entry.req_ext[k] = e.re[k];
+            from_entry.qos = e.qos; from_entry.priority = e.priority; from_entry.app = e.app;
+            p = &from_entry;
+        }
         if (!p) fail(QS_EINVAL, "null pod");
         if (node >= c->m.n) fail(QS_EINVAL, "node index out of range");
         check_pod(*p, 0);
@@ -2254,6 +2436,16 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
             // (k_aa_apply below maintains them)
             if (pod_host_spread(*p) && c->dev_valid) ensure_hcount(c);
         }
+        if (c->preempt_on && sign < 0 && evict_seq == 0) {
+            // the registry entry this Unreserve removes (spec S18): the latest one that equals the pod
+            reg_at = reg_find(c, node, p, 0);
+            if (reg_at < 0)
+                fail(QS_EINVAL, "qs_unreserve: no registered pod of node " + std::to_string(node) + " equals this pod");
+        }
+        auto reg_record = [&] {  // (last: nothing after it fails)
+            if (reg_at >= 0) reg_erase(c, node, (size_t)reg_at);
+            else if (c->preempt_on && sign > 0) reg_append(c, node, *p);
+        };
         sync_mirror(c);
         const RowSnap before = snap_row(c->m, node);
         mirror_reserve(c->m, node, *p, sign);
@@ -2290,6 +2482,7 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
                     c->pend = pend_before;
                     throw;
                 }
+                reg_record();
                 return;
             }
             flush_pending(c);
@@ -2299,6 +2492,7 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
             ensure_layout(c, p, 1);
             if (was_valid && c->shift == old_shift && c->wide == old_wide) push_row(c, node);
             aa_record();
+            reg_record();
         } catch (...) {
             put_row(c->m, node, before);
             throw;
@@ -2307,6 +2501,116 @@ static qs_status reserve_impl(qs_ctx *c, uint32_t node, const qs_pod *p, int sig
 }
 qs_status qs_reserve(qs_ctx *c, uint32_t node, const qs_pod *p) { return reserve_impl(c, node, p, +1); }
 qs_status qs_unreserve(qs_ctx *c, uint32_t node, const qs_pod *p) { return reserve_impl(c, node, p, -1); }
+
+// ---- preemption (spec S18) ----
+qs_status qs_evict(qs_ctx *c, uint32_t node, uint64_t seq) {
+    if (seq == 0) {
+        if (!c) return QS_EINVAL;
+        return guarded(c, [&] { fail(QS_EINVAL, "qs_evict: seq 0 names no entry"); }, /*keep_pending=*/true);
+    }
+    return reserve_impl(c, node, nullptr, -1, seq);
+}
+
+qs_status qs_set_preemption(qs_ctx *c, int32_t on) {
+    return guarded(c, [&] {
+        if (!c->streams.empty()) fail(QS_ESTATE, "the pod registry cannot be switched while prepared streams exist");
+        if (on) {
+            if (c->world > 1 || c->cfg.virtual_shards > 1)
+                fail(QS_EINVAL, "the pod registry runs unsharded (qs_open_shard / virtual_shards > 1)");
+            if (c->m.n > kRegMaxNodes) fail(QS_EINVAL, "the pod registry covers tables up to 2^17 nodes");
+        }
+        c->preempt_on = on != 0;  // (what is registered stays as it is)
+    });
+}
+
+qs_status qs_get_preemption(qs_ctx *c, int32_t *on) {
+    return guarded(c, [&] {
+        if (!on) fail(QS_EINVAL, "null output");
+        *on = c->preempt_on ? 1 : 0;
+    });
+}
+
+qs_status qs_set_preemption_policy(qs_ctx *c, int32_t policy) {
+    return guarded(c, [&] {
+        if (policy != QS_PREEMPT_BY_PRIORITY && policy != QS_PREEMPT_BY_QOS) fail(QS_EINVAL, "unknown qs_preempt_policy");
+        if (policy == c->preempt_policy) return;
+        c->preempt_policy = policy;
+        // (the saved registry follows when it is restored: qs_table_restore sorts what it reinstates)
+        reg_resort(c);
+    });
+}
+
+qs_status qs_get_preemption_policy(qs_ctx *c, int32_t *policy) {
+    return guarded(c, [&] {
+        if (!policy) fail(QS_EINVAL, "null output");
+        *policy = c->preempt_policy;
+    });
+}
+
+qs_status qs_node_pods(qs_ctx *c, uint32_t node, qs_victim *out, uint32_t cap, uint32_t *n) {
+    return guarded(c, [&] {
+        if (!n || (cap && !out)) fail(QS_EINVAL, "null output");
+        if (node >= c->m.n) fail(QS_EINVAL, "node index out of range");
+        *n = 0;
+        if (node >= c->m.reg.size()) return;
+        const auto &l = c->m.reg[node];
+        *n = (uint32_t)l.size();
+        for (uint32_t k = 0; k < l.size() && k < cap; k++) out[k] = reg_victim(l[k]);
+    }, /*keep_pending=*/true);
+}
+
+qs_status qs_preempt_pod(qs_ctx *c, const qs_pod *pod, int32_t *node, qs_victim *victims, uint32_t *n_victims,
+                         int32_t *nvict_n) {
+    return guarded(c, [&] {
+        if (!pod || !node || !victims || !n_victims) fail(QS_EINVAL, "null argument");
+        if (!c->preempt_on) fail(QS_ESTATE, "the pod registry is off (qs_set_preemption)");
+        check_pod(*pod, 0);
+        if (c->aa_track && QS_AA_KIND(pod->anti_affinity) != QS_AA_NONE)
+            fail(QS_EINVAL, "preemption for a pod with anti-affinity or topology spread on a context that tracks them "
+                            "is not built (spec S18): removing victims would change the counts its filter reads");
+        const uint32_t n = c->m.n;
+        if (n > kRegMaxNodes) fail(QS_EINVAL, "the pod registry covers tables up to 2^17 nodes");
+        *node = -1;
+        *n_victims = 0;
+        if (n == 0) return;
+        if (c->reg_long)
+            for (uint32_t i = 0; i < c->m.reg.size(); i++)
+                if (c->m.reg[i].size() > QS_MAX_VICTIMS)
+                    fail(QS_EINVAL, "node " + std::to_string(i) + " holds " + std::to_string(c->m.reg[i].size()) +
+                                        " registered pods, more than QS_MAX_VICTIMS");
+        HIPCHK(hipSetDevice(c->device));
+        if (!c->dev_valid) upload_table(c);  // recovery after a device fault: rebuild from the mirror
+        reg_sync_device(c);
+        // the preemptor in canonical units: the dry run needs no layout the pod fits
+        const DPodX dx = compact_podx(c, *pod);
+        PreemptPod pp{pod->req_cpu, pod->req_mem, pod->req_ext[0], pod->req_ext[1],
+                      reg_importance(c->preempt_policy, pod->qos, pod->priority), pod_flags(c, *pod), c->wide ? 0 : c->shift};
+        constexpr size_t kOutBytes = (sizeof(PreemptOut) + 15) & ~(size_t)15;
+        c->reg_out.ensure(kOutBytes + sizeof(DPodX));
+        c->reg_rec.ensure(preempt_scratch_bytes());
+        if (nvict_n) c->reg_nv.ensure((size_t)c->cap * 4);
+        DPodX *dpx = reinterpret_cast<DPodX *>(c->reg_out.as<char>() + kOutBytes);
+        HIPCHK(hipMemcpyAsync(dpx, &dx, sizeof dx, hipMemcpyHostToDevice, c->stream));
+        const uint64_t *col = c->reg_dev.as<uint64_t>();
+        const RegView rv{col, reinterpret_cast<const uint32_t *>(col + (size_t)kRegCols * c->reg_slots * c->reg_cap),
+                         c->reg_slots, c->reg_cap};
+        HIPCHK(launch_preempt(c->dt, c->wide, rv, pp, dpx, nvict_n ? c->reg_nv.as<int32_t>() : nullptr, c->reg_rec.p,
+                              c->reg_out.as<PreemptOut>(), c->stream));
+        PreemptOut po;
+        HIPCHK(hipMemcpyAsync(&po, c->reg_out.p, sizeof po, hipMemcpyDeviceToHost, c->stream));
+        if (nvict_n) HIPCHK(hipMemcpyAsync(nvict_n, c->reg_nv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (po.node < 0) return;
+        if ((uint32_t)po.node >= n || po.nvict > QS_MAX_VICTIMS) fail(QS_EDEVICE, "preemption dry run returned a record out of range");
+        const auto &l = c->m.reg[(uint32_t)po.node];
+        for (uint32_t k = 0; k < po.nvict; k++) {
+            if (po.slot[k] >= l.size()) fail(QS_EDEVICE, "preemption dry run returned a slot out of range");
+            victims[k] = reg_victim(l[po.slot[k]]);
+        }
+        *node = po.node;
+        *n_victims = po.nvict;
+    });
+}
 
 // The packed outputs of the one-launch score (pinned host memory, written by the kernel: one u32 of
 // four byte scores per node, 0xFFFFFFFF = infeasible) into the caller's arrays, 16 nodes per step as
@@ -2803,7 +3107,8 @@ qs_status qs_table_restore(qs_ctx *c) {
         write_spread_cfg(c);      // (the snapshot holds the topology spread weight of its save, and the
                                   // address of the (app, node) counts of its save)
         c->hc_valid = false;      // (rebuilt from the mirror reinstated below, spec S15)
-        c->m = c->m_saved;        // the mirror of the snapshot
+        c->m = c->m_saved;        // the mirror of the snapshot (the pod registry and its counter with it, spec S18)
+        reg_resort(c);            // (under the policy of now)
         c->zero_alloc = count_zero_alloc(c->m);
         c->mirror_stale = false;
         ++c->table_epoch;
@@ -2851,6 +3156,7 @@ size_t qs_struct_size(int which) {
         case 4: return sizeof(qs_container);
         case 5: return sizeof(qs_stats);
         case 6: return sizeof(qs_scoring_strategy);
+        case 7: return sizeof(qs_victim);
         default: return 0;
     }
 }

@@ -157,6 +157,46 @@ hipError_t launch_batch_claim(const DevTable &t, const void *pods, const uint64_
                               uint32_t *bidx, uint32_t P, uint32_t B, int32_t *out_node,
                               uint64_t *out_key, hipStream_t stream);
 
+// ---- preemption dry run (spec S18; qs_kernels_preempt.hip) ----------------------
+// Device copy of the pod registry, slot-major: column k (kRegCols of them, canonical int64 / uint64
+// quantities) of slot s of node i at col[(k * slots + s) * cap + i], so a wave over 64 consecutive
+// nodes reads consecutive addresses per slot; len[i] entries per node, sorted as the dry run walks them.
+enum RegCol : uint32_t { kRegImp, kRegSeq, kRegCpu, kRegMem, kRegExt0, kRegExt1, kRegCols };
+struct RegView {
+    const uint64_t *col;
+    const uint32_t *len;
+    uint32_t slots, cap;
+};
+// The preemptor: canonical requests, its importance, its pod flags (pod_flags: the required-term
+// count feasible() reads) and the table's memory unit (compact layout; 0 in the wide one).
+struct PreemptPod {
+    int64_t rc, rm, re0, re1;
+    uint64_t imp;
+    uint32_t flags;
+    int32_t shift;
+};
+constexpr uint32_t kPreemptMaxVictims = 256;  // QS_MAX_VICTIMS
+// What the pick launch leaves: the chosen node (-1: no candidate) and its victims' slot numbers in walk order.
+struct PreemptOut {
+    int32_t node;
+    uint32_t nvict;
+    uint32_t slot[kPreemptMaxVictims];
+};
+// One registry entry on its way to the device copy (k_preempt_scatter): node, slot and the kRegCols values.
+struct RegItem {
+    uint32_t node, slot;
+    uint64_t v[kRegCols];
+};
+size_t preempt_scratch_bytes();  // the per-workgroup candidate records between the two launches
+// k_preempt_nodes (one lane per node, one candidate record per workgroup) then k_preempt_pick (one
+// workgroup: the choice and the winner's victims) on `stream`.  nvict_n nullable (n entries otherwise).
+hipError_t launch_preempt(const DevTable &t, bool wide, const RegView &rv, const PreemptPod &pp, const DPodX *px,
+                          int32_t *nvict_n, void *scratch, PreemptOut *out, hipStream_t stream);
+// items -> the device copy (m of them), lens -> len[] of the nodes listed in lnode (k of them)
+hipError_t launch_preempt_scatter(uint64_t *col, uint32_t *len, uint32_t slots, uint32_t cap, const RegItem *items,
+                                  uint32_t m, const uint32_t *lnode, const uint32_t *lval, uint32_t k,
+                                  hipStream_t stream);
+
 __global__ void k_set_row(DevTable t, uint32_t i, HostRow v, uint32_t feat);
 // Reserve (sign +1) / Unreserve (-1) of one pod of `app` on `node` in the anti-affinity state
 // (spec S12): sets the presence bit, or clears it when clear_bit, and moves the (app, zone) count.

@@ -32,6 +32,11 @@ __all__ = ["Scheduler", "Config", "POD_DTYPE", "pods_to_struct", "pods_from_stru
 from ._abi import (QS_POLICY_HONOR, QS_POLICY_IGNORE, QS_AA_HOSTKEY, QS_AA_HOSTNAME, QS_AA_NONE, QS_AA_SOFT, QS_AA_SPREAD_ZONE, QS_AA_ZONE,  # noqa: E402,F401
                    QS_MAX_SPREAD_SKEW, QS_MAX_ZONES)
 
+from ._abi import (PREEMPT_POLICIES, QS_MAX_VICTIMS, QS_PREEMPT_BY_PRIORITY, QS_PREEMPT_BY_QOS,  # noqa: E402,F401
+                   VICTIM_DTYPE)
+
+__all__ += ["VICTIM_DTYPE", "QS_MAX_VICTIMS", "QS_PREEMPT_BY_PRIORITY", "QS_PREEMPT_BY_QOS", "PREEMPT_POLICIES"]
+
 MODES = {"exact": QS_MODE_EXACT, "batched": QS_MODE_BATCHED}
 POLICIES = {"ignore": QS_POLICY_IGNORE, "honor": QS_POLICY_HONOR}
 
@@ -361,6 +366,54 @@ class Scheduler:
     def unreserve(self, node, pod):
         p = pods_to_struct(pod) if not isinstance(pod, np.void) else np.array([pod], POD_DTYPE)
         self._chk(self.lib.qs_unreserve(self.ctx, node, _ptr(p)))
+
+    # ---- preemption (spec S18) ----
+    def set_preemption(self, on=True):
+        """qs_set_preemption: the pod registry (which pods sit on which node); off in a new context."""
+        self._chk(self.lib.qs_set_preemption(self.ctx, 1 if on else 0))
+
+    def get_preemption(self) -> bool:
+        on = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_preemption(self.ctx, ctypes.byref(on)))
+        return bool(on.value)
+
+    def set_preemption_policy(self, policy):
+        """qs_set_preemption_policy: "priority" (upstream's rule; a new context) or "qos" (QoS class, then
+        priority: the order of spec S8), or a QS_PREEMPT_* value."""
+        pol = PREEMPT_POLICIES[policy] if isinstance(policy, str) else int(policy)
+        self._chk(self.lib.qs_set_preemption_policy(self.ctx, pol))
+
+    def get_preemption_policy(self) -> int:
+        v = ctypes.c_int32(-1)
+        self._chk(self.lib.qs_get_preemption_policy(self.ctx, ctypes.byref(v)))
+        return int(v.value)
+
+    def node_pods(self, node):
+        """qs_node_pods: the node's registry entries as a VICTIM_DTYPE array, most important first."""
+        n = ctypes.c_uint32(0)
+        self._chk(self.lib.qs_node_pods(self.ctx, node, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, VICTIM_DTYPE)
+        if n.value:
+            self._chk(self.lib.qs_node_pods(self.ctx, node, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def preempt_pod(self, pod, per_node=False):
+        """qs_preempt_pod: (node, victims) of the dry run for one pod, node -1 without a candidate and
+        victims a VICTIM_DTYPE array in walk order; with per_node also the victims per node (int32[n], -1
+        where the node is no candidate).  Changes no state: evict() the victims, then reserve()."""
+        p = np.array([pod], POD_DTYPE) if isinstance(pod, np.void) else pods_to_struct(pod)[:1]
+        node = ctypes.c_int32(-2)
+        nv = ctypes.c_uint32(0)
+        victims = np.zeros(QS_MAX_VICTIMS, VICTIM_DTYPE)
+        nvict_n = np.full(self.n, -2, np.int32) if per_node else None
+        self._chk(self.lib.qs_preempt_pod(self.ctx, _ptr(p), ctypes.byref(node), _ptr(victims), ctypes.byref(nv),
+                                          _ptr(nvict_n)))
+        res = (int(node.value), victims[:nv.value].copy())
+        return res + (nvict_n,) if per_node else res
+
+    def evict(self, node, seq):
+        """qs_evict: remove the registry entry `seq` of `node` (Unreserve with the recorded requests)."""
+        self._chk(self.lib.qs_evict(self.ctx, int(node), int(seq)))
 
     # ---- one pod, all nodes ----
     def score_pod(self, pod, outputs=True, out=None):

@@ -144,6 +144,16 @@ POD_DTYPE = np.dtype([
     ("pref_weight", "<i4", (QS_MAX_TERMS,)), ("app", "<i4"), ("anti_affinity", "<i4"),
 ], align=True)
 
+# qs_victim as a numpy structured dtype (72 bytes): one pod registry entry / one victim (spec S18)
+VICTIM_DTYPE = np.dtype([
+    ("seq", "<u8"), ("req_cpu", "<i8"), ("req_mem", "<i8"), ("req_ext", "<i8", (QS_MAX_EXT,)),
+    ("nz_cpu", "<i8"), ("nz_mem", "<i8"), ("priority", "<i4"), ("qos", "<i4"), ("app", "<i4"),
+    ("reserved", "<i4"),
+], align=True)
+QS_MAX_VICTIMS = 256
+QS_PREEMPT_BY_PRIORITY, QS_PREEMPT_BY_QOS = 0, 1  # qs_preempt_policy (spec S18 "Importance")
+PREEMPT_POLICIES = {"priority": QS_PREEMPT_BY_PRIORITY, "qos": QS_PREEMPT_BY_QOS}
+
 _P = ctypes.c_void_p
 _SIGS = {
     "qs_config_default": (None, [_P]),
@@ -164,6 +174,13 @@ _SIGS = {
     "qs_set_topology_spread_node_taints_policy": (ctypes.c_int, [_P, ctypes.c_int32]),
     "qs_get_topology_spread_node_taints_policy": (ctypes.c_int, [_P, _P]),
     "qs_score_pod_zone_scores": (ctypes.c_int, [_P, _P]),
+    "qs_set_preemption": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "qs_get_preemption": (ctypes.c_int, [_P, _P]),
+    "qs_set_preemption_policy": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "qs_get_preemption_policy": (ctypes.c_int, [_P, _P]),
+    "qs_node_pods": (ctypes.c_int, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, _P]),
+    "qs_preempt_pod": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "qs_evict": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint64]),
     "qs_shape_table": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "qs_close": (ctypes.c_int, [_P]),
     "qs_last_error": (ctypes.c_char_p, [_P]),
@@ -212,7 +229,7 @@ def load(path: str = LIB_PATH):
         fn.argtypes = args
     expect = {0: ctypes.sizeof(QsConfig), 1: ctypes.sizeof(QsNodeSoa), 2: ctypes.sizeof(QsNodeRow),
               3: POD_DTYPE.itemsize, 4: ctypes.sizeof(QsContainer), 5: ctypes.sizeof(QsStats),
-              6: ctypes.sizeof(QsScoringStrategy)}
+              6: ctypes.sizeof(QsScoringStrategy), 7: VICTIM_DTYPE.itemsize}
     for k, v in expect.items():
         got = lib.qs_struct_size(k)
         if got != v:

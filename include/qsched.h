@@ -23,6 +23,9 @@
  *                             ScoreExtensions}; UP schedule_one.go#{findNodesThatPassFilters,prioritizeNodes})
  *   qs_reserve / qs_unreserve ReservePlugin.Reserve / Unreserve → NodeInfo.AddPod / RemovePod
  *                             (UP framework/interface.go#ReservePlugin, framework/types.go#NodeInfo.update)
+ *   qs_preempt_pod / qs_evict PostFilter of DefaultPreemption: the dry run over every node and the choice
+ *                             (UP plugins/defaultpreemption#SelectVictimsOnNode, framework/preemption/
+ *                             preemption.go#pickOneNodeForPreemption; spec/semantics.md S18)
  *   qs_schedule_stream        ScheduleOne loop with deterministic selectHost (UP schedule_one.go#
  *                             {ScheduleOne,schedulingCycle,selectHost,assume}; spec/semantics.md S7/S8)
  *
@@ -405,6 +408,58 @@ QS_API qs_status qs_table_restore(qs_ctx *ctx);
 QS_API qs_status qs_reserve(qs_ctx *ctx, uint32_t node, const qs_pod *pod);
 QS_API qs_status qs_unreserve(qs_ctx *ctx, uint32_t node, const qs_pod *pod);
 
+/* ---- preemption dry run (spec S18) ----
+ * The pod registry: which pods sit on which node, per context, off in a new context (nothing is recorded
+ * and no call changes while it is off; replaces the per-node pod lists of UP framework/types.go#NodeInfo.Pods
+ * that UP plugins/defaultpreemption reads).  While it is on, qs_reserve appends the pod it reserves to the
+ * node's list and every stream, exact or batched, appends its placed pods in the stream's decision order
+ * (on the host after the run, outside wall_s).  An entry carries seq, a context-wide counter from 1 (the
+ * stand-in for upstream's pod StartTime), and the pod's priority, qos, app and requests.  Load that
+ * qs_nodes_load or qs_node_upsert brought belongs to no entry and is never freed by preemption.
+ * qs_nodes_load empties the registry; qs_table_save / qs_table_restore cover it, the counter included;
+ * switching it on or off does not clear it.  With the registry on, qs_unreserve removes the entry of the
+ * node with the highest seq whose fields equal the pod's (QS_EINVAL, nothing changed, when there is none),
+ * and a qs_node_upsert whose requested columns or pod count fall below the sums over the node's entries
+ * is QS_EINVAL.  QS_ESTATE while the context holds prepared streams; QS_EINVAL (switching on) on a
+ * sharded context (qs_open_shard, virtual_shards > 1) or a table above 2^17 nodes, and for null pointers. */
+QS_API qs_status qs_set_preemption(qs_ctx *ctx, int32_t on);
+QS_API qs_status qs_get_preemption(qs_ctx *ctx, int32_t *on);
+/* How pods rank against each other (spec S18 "Importance"), one policy per context.
+ * QS_PREEMPT_BY_PRIORITY (a new context) is upstream's rule, the pod's priority alone
+ * (UP framework/preemption/preemption.go, util.MoreImportantPod); QS_PREEMPT_BY_QOS ranks by QoS class
+ * first, then priority: the order of spec S8 (QoSSort).  QS_EINVAL for an unknown policy or a null pointer. */
+typedef enum qs_preempt_policy { QS_PREEMPT_BY_PRIORITY = 0, QS_PREEMPT_BY_QOS = 1 } qs_preempt_policy;
+QS_API qs_status qs_set_preemption_policy(qs_ctx *ctx, int32_t policy);
+QS_API qs_status qs_get_preemption_policy(qs_ctx *ctx, int32_t *policy);
+/* One registry entry: a pod on a node, and a victim of a dry run. */
+typedef struct qs_victim {
+    uint64_t seq;
+    int64_t req_cpu, req_mem, req_ext[QS_MAX_EXT], nz_cpu, nz_mem;
+    int32_t priority, qos, app, reserved;
+} qs_victim; /* qs_struct_size(7) */
+#define QS_MAX_VICTIMS 256
+/* The node's entries, most important first (importance descending, then seq ascending: the order of the
+ * dry run's reprieve walk, UP util.MoreImportantPod over NodeInfo.Pods): *n = their number, of which the
+ * first min(*n, cap) are written to out (nullable when cap = 0).  QS_EINVAL for a node outside the table. */
+QS_API qs_status qs_node_pods(qs_ctx *ctx, uint32_t node, qs_victim *out, uint32_t cap, uint32_t *n);
+/* The dry run for one pod over ALL nodes in one device pass (replaces UP plugins/defaultpreemption#
+ * DefaultPreemption.PostFilter: framework/preemption#Evaluator.{findCandidates, DryRunPreemption},
+ * defaultpreemption#SelectVictimsOnNode without PodDisruptionBudgets, and preemption.go#
+ * pickOneNodeForPreemption; no candidate sampling, every node is evaluated).  *node = the chosen node or
+ * -1; victims[QS_MAX_VICTIMS] / *n_victims = its victims in walk order; nvict_n (nullable, n entries) =
+ * victims per node, -1 where the node is no candidate.  The call changes no state: the caller evicts
+ * (qs_evict) and reserves.  QS_ESTATE with the registry off; QS_EINVAL for a pod qs_reserve would reject,
+ * for a pod with an anti_affinity kind other than QS_AA_NONE on a context that tracks pod anti-affinity
+ * (removing victims would change the counts its filter reads), and when a node holds more than
+ * QS_MAX_VICTIMS entries (the message names the node). */
+QS_API qs_status qs_preempt_pod(qs_ctx *ctx, const qs_pod *pod, int32_t *node, qs_victim *victims,
+                                uint32_t *n_victims, int32_t *nvict_n);
+/* Removes the entry `seq` of `node` (the caller has deleted that pod: UP framework/preemption#
+ * Evaluator.prepareCandidate -> util.DeletePod, then NodeInfo.RemovePod): Unreserve with the recorded
+ * requests and, with anti-affinity tracking on, of the recorded app, as qs_unreserve does.  QS_EINVAL
+ * when the node holds no such entry. */
+QS_API qs_status qs_evict(qs_ctx *ctx, uint32_t node, uint64_t seq);
+
 /* ---- one pod, all nodes (framework-embedded path) ----
  * feasible_n (nullable): 1/0 per node; score_n (nullable): [n][4] {LeastAllocated, Balanced,
  * TaintToleration, NodeAffinity} normalized plugin scores (0 where infeasible); total_n (nullable):
@@ -479,7 +534,7 @@ QS_API qs_status qs_pod_from_containers(const qs_container *c, uint32_t nc, cons
                                  qs_pod *out);
 QS_API int32_t qs_compute_qos(const qs_container *c, uint32_t nc);
 /* sizeof of the ABI structs for binding self-checks: 0 config, 1 node_soa, 2 node_row, 3 pod,
- * 4 container, 5 stats, 6 scoring_strategy. */
+ * 4 container, 5 stats, 6 scoring_strategy, 7 victim. */
 QS_API size_t qs_struct_size(int which);
 /* The shape function of RequestedToCapacityRatio as a table (no context): validates the shape as
  * qs_set_scoring_strategy does and writes table[p] = raw(p) * 10 for the utilisation p = 0..100
